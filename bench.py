@@ -325,6 +325,24 @@ def _time_steps(fn, build, warmup, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this much per node
+
+
+def dump_outputs(d, wavs, owned, budget):
+    """Writes waveform k as d/wav_<owned[k]>.npy (float32, the utterance's global index, as the caller received it).  When
+    they come to more than `budget` bytes, every waveform is cut down to the same fraction of its samples, at positions
+    drawn by a generator seeded with its index: two runs of the same arguments write the same positions."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrs = [w.detach().float().cpu().numpy() for w in wavs]
+    total, room = sum(x.nbytes for x in arrs), budget - 128 * len(arrs)          # 128: the .npy header of a 1-3 d array
+    for gi, x in zip(owned, arrs):
+        if total > room:
+            k = x.size * room // total
+            x = x.reshape(-1)[np.sort(np.random.default_rng(gi).choice(x.size, k, replace=False))]
+        np.save(os.path.join(d, f"wav_{gi:04d}.npy"), x)
+
+
 ATTN = "bf16"
 GROUP_FAN = None
 FLOW_PRIO = None
@@ -377,7 +395,12 @@ def main():
     ap.add_argument("--no-polite", action="store_true", help="flow groups beside the decode loop use the fastest tiling instead of the 64-row one")
     ap.add_argument("--tail-active", type=int, default=0, help="with at most this many sequences still decoding, finished utterances go to an idle flow worker at once")
     ap.add_argument("--no-overlap", action="store_true", help="run LM decode and flow/DAC back to back (one stream)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the waveforms of the last timed step as DIR/wav_<utterance>.npy (float32; "
+                         "each rank its own utterances; beyond 64 MB per node a fixed, seeded sample of every waveform)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     global ATTN, GROUP_FAN, FLOW_PRIO, CKPT_KIND
     ATTN, GROUP_FAN, FLOW_PRIO, CKPT_KIND = a.attn, a.group_fan, a.flow_priority, a.checkpoint
     if a.lm_planes:
@@ -466,22 +489,30 @@ def main():
 
     first_chunk_ms = []
 
-    def step():
+    def step(keep=None):
+        """One pass over the rank's utterances; returns the samples generated.  `keep`, a list: receives the waveforms the
+        caller of the path gets (the streamed chunks of one utterance joined), for --dump-outputs."""
         if a.workload == "longform":
             if have_gpu:
                 torch.cuda.synchronize()       # a new request on an idle device: the first-chunk latency is measured from here
             t_in = time.perf_counter()
-            n = 0
+            n, chunks = 0, []
             for k, w in enumerate(eng.tts_stream(texts[0], emb, seed=0, exact_steps=lens[0])):
                 if k == 0:
                     if have_gpu:
                         torch.cuda.current_stream().synchronize()
                     first_chunk_ms.append((time.perf_counter() - t_in) * 1e3)
                 n += w.shape[-1]
+                if keep is not None:
+                    chunks.append(w.clone())          # a chunk may be a view of a buffer the next hop reuses
+            if keep is not None:
+                keep.append(torch.cat(chunks, dim=-1))
             return n
         wavs = eng.tts_batch(texts, [emb] * len(texts), seed=0, exact_steps=lens, group_size=[int(v) for v in str(a.flow_group).split(',')], overlap=not a.no_overlap, max_pad_ratio=a.pad_ratio, flow_workers=a.flow_workers, hold_steps=a.hold_steps, poll_every=a.poll_every, tail_active=a.tail_active, polite=not a.no_polite)
         if world > 1:                                              # the path's one exchange step (RCCL all-gather)
             gather_audio([w.cpu() for w in wavs] if rehearse else wavs, mine, len(lens_all))
+        if keep is not None:
+            keep.extend(wavs)
         return sum(w.shape[-1] for w in wavs)
 
     def fence():
@@ -510,10 +541,13 @@ def main():
     fence()
     t0 = time.perf_counter()
     samples = 0
-    for _ in range(a.steps):
-        samples += step()
+    last = [] if a.dump_outputs else None
+    for i in range(a.steps):
+        samples += step(last if i == a.steps - 1 else None)
     fence()
     el = time.perf_counter() - t0
+    if last is not None:
+        dump_outputs(a.dump_outputs, last, mine, DUMP_BYTES // world)
     for fl in flows:
         fl.shape_log = None
     if world > 1:

@@ -186,6 +186,77 @@ def test_bench_two_rank_rehearsal_gloo(tmp_path):
     assert abs(j["config"]["audio_s_per_step"] - sum(lens) / 25.0) < 0.01          # both ranks' utterances are counted
 
 
+_DUMP_WORKER = r"""
+import json, os, sys, numpy as np, torch
+root, out = sys.argv[1], sys.argv[2]
+sys.path.insert(0, root)
+import bench
+
+
+class StubEngine:
+    # a waveform per utterance that depends on its text ids and on the call: the dump must be the LAST timed call's output
+    calls = 0
+
+    def tts_batch(self, texts, embs, seed=0, exact_steps=None, **kw):
+        StubEngine.calls += 1
+        g = torch.Generator().manual_seed(int(sum(t.sum() for t in texts)) + StubEngine.calls)
+        self.last = [torch.randn(1, 1, 2 * n * 480, generator=g) for n in exact_steps]
+        return self.last
+
+
+eng = StubEngine()
+bench.make_engine = lambda dt, device, max_batch, max_ctx: eng
+if len(sys.argv) > 3:
+    bench.DUMP_BYTES = int(sys.argv[3])
+sys.argv = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--per-gpu", "4", "--no-cpu-baseline", "--no-extras",
+            "--no-roofline", "--dump-outputs", out]
+bench.main()
+np.savez(os.path.join(out, "..", os.path.basename(out) + "_stub.npz"), *[w.numpy() for w in eng.last])
+print("calls", StubEngine.calls)
+"""
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs (stub engine, no GPU): --steps timed calls after the 2 build passes and --warmup; the dump is the
+    last timed call's waveforms, float32, one file per utterance (global index); the same arguments give the same files; over
+    the size budget every waveform becomes a seeded sample of itself, within the budget and the same from run to run."""
+    import numpy as np
+    from mmx.dist import shard_utterances
+    script = tmp_path / "d.py"
+    script.write_text(_DUMP_WORKER)
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+
+    def run(name, *extra):
+        p = subprocess.run([sys.executable, str(script), ROOT, str(tmp_path / name), *extra], capture_output=True, env=env, timeout=180)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        lines = p.stdout.decode().splitlines()
+        return json.loads([l for l in lines if l.startswith("{")][0]), lines[-1]
+
+    lens = torch.randint(50, 501, (4,), generator=torch.Generator().manual_seed(3)).tolist()
+    mine = shard_utterances(lens, 1)[0]
+    j, calls = run("a")
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and calls == "calls 6"
+    stub = np.load(tmp_path / "a_stub.npz")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == [f"wav_{i:04d}.npy" for i in range(4)]
+    for k, gi in enumerate(mine):
+        x = np.load(tmp_path / "a" / f"wav_{gi:04d}.npy")
+        assert x.dtype == np.float32 and x.shape == (1, 1, 2 * lens[gi] * 480)
+        assert np.array_equal(x, stub[f"arr_{k}"])
+    run("b")
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+    budget = 200_000
+    for d in ("c", "d"):
+        run(d, str(budget))
+        assert sorted(os.listdir(tmp_path / d)) == names
+        assert sum(os.path.getsize(tmp_path / d / n) for n in names) <= budget
+    for n in names:
+        full, c = np.load(tmp_path / "a" / n), np.load(tmp_path / "c" / n)
+        assert c.dtype == np.float32 and c.ndim == 1 and 0 < c.size < full.size and np.isin(c, full).all()
+        assert np.array_equal(c, np.load(tmp_path / "d" / n))
+
+
 def test_scheduler_cost_model_refit():
     """TtsEngine._refit_sched (host logic of tts_batch): the fit of (decode step, group cost = a + b * frames) from a call's own
     events; calls that captured plans are ignored; with sched_adapt the model follows two agreeing steady fits past the hysteresis."""
