@@ -11,6 +11,7 @@ MFMA flash-attention kernel reads K row-major and V^T row-major without any tran
 A whole 10-step Euler solve (about 5 000 launches) is recorded once per shape into a hipGraph.
 """
 import gc
+import itertools
 import math
 from collections import OrderedDict
 from typing import Dict, Optional
@@ -193,7 +194,6 @@ class FlowEngine:
             self.close()                                   # recorded plans baked the old noise in
 
     def _init_encoder(self, sd, f, lin, cv):
-        dt = self.dtype
         flow_level = "input_embedding.weight" in sd          # absent when built for a bare UpsampleConformerEncoder
         if flow_level:
             self.emb_table = f("input_embedding.weight")
@@ -219,9 +219,6 @@ class FlowEngine:
                 w1=lin(p + ".feed_forward.w_1.weight"), b1=f(p + ".feed_forward.w_1.bias"),
                 w2=lin(p + ".feed_forward.w_2.weight"), b2=f(p + ".feed_forward.w_2.bias"))
 
-        # bf16 build: rel-pos attention on the MFMA (mmx_attn_relpos_bf16) - Q | K rows from one GEMM, V^T from a second one
-        # with the weights as its A operand (the layout the flash kernels read); other builds: mmx_attn_dense (fp32 VALU)
-        self.enc_mfma = dt == BF16 and getattr(self, "enc_attn", "mfma") == "mfma"
         self.enc = dict(embed=embed(e + ".embed"), up_embed=embed(e + ".up_embed"),
                         pl_w1=cv(e + ".pre_lookahead_layer.conv1.weight"), pl_b1=f(e + ".pre_lookahead_layer.conv1.bias"),
                         pl_w2=cv(e + ".pre_lookahead_layer.conv2.weight"), pl_b2=f(e + ".pre_lookahead_layer.conv2.bias"),
@@ -309,43 +306,49 @@ class FlowEngine:
         return self._pe[T]
 
     # ------------------------------------------------------------------ encoder
-    def _conformer(self, lw, x, T, pos_act, chunk, B=1, klen=None, keymask=None):
-        """One conformer layer on x fp32 [B * T, 512] (B utterances zero padded to T rows each; klen int32 [B] / keymask fp32
-        [B, T]: the valid rows - the rows beyond them carry finite garbage that no valid row ever reads)."""
-        dt = self.dtype
-        R = B * T
+    def _conformer(self, lw, x, T, chunk, pe=None, B=1, klen=None, keymask=None, qkv=None, pos=None, t0=0):
+        """One ConformerEncoderLayer on x fp32 [B * (T - t0), 512] (returned likewise).  Whole sequences (qkv None): B
+        utterances zero padded to T rows each, rel-pos table pe [2T - 1, 512] projected here; klen int32 [B] / keymask fp32
+        [B, T]: the valid rows (the rows beyond them carry finite garbage that no valid row ever reads).  bf16 build: the
+        attention on the MFMA (mmx_attn_relpos_bf16) - Q | K rows from one GEMM, V^T from a second one with the weights as
+        its A operand (the layout the flash kernels read); split build: the same with every operand as bf16 hi + lo
+        (mmx_attn_relpos_x); fp32 build: mmx_attn_dense.  Streaming rows (B = 1): rows t0 .. T-1 only; qkv [Tcap, 1536]
+        holds the Q | K | V rows of ALL positions (this call writes rows t0 .. T-1), pos the projected table of the capacity
+        with its base shifted so that the kernel's pos[T - 1 - i + j] is relative distance i - j; mmx_attn_dense."""
+        dt, R = self.dtype, B * (T - t0)
         hn = self._new(R, 512)
         ops.rownorm(x, lw["n1g"], lw["n1b"], 1e-12, rows=R, C_=512, out_act=hn, dtype=dt)
-        p = self._new(2 * T - 1, 512)
-        ops.linear(pos_act, lw["wpos"], 512, dtype=dt, out_act=p)
-        ao = self._new(R, 512)
-        if self.enc_mfma:
+        dense = qkv is not None or not (dt == BF16 or self.split)
+        if pos is None:
+            pos = self._new(2 * T - 1, 512)
+            ops.linear(pe, lw["wpos"], 512, dtype=dt, out_act=pos)
+        ao = self._new(B * T, 512)
+        if dt == BF16 and not dense:
             qk = self._new(R, 1024)
             ops.linear(hn, lw["wqkv"][:1024], 512, dtype=dt, bias=lw["bqkv"][:1024], out_act=qk)
             Tp = ops.round_up(T, 8)
-            vt = self._new(B, 512, Tp)                        # [B][512][Tp]; not from the plan-lifetime cache (_vt_buf):
+            vt = self._new(B, 512, Tp)                        # [B][512][Tp]; not from the plan-lifetime cache (_attn_bufs):
             if Tp > T:                                        # an encoder call's shape is arbitrary, the cache would only grow
                 vt[:, :, T:].zero_()                          # pad columns must be finite: the flash tiles read 8 at a time
             ops.gemm(lw["wqkv"][1024:], hn, 512, T, dtype=dt, lda=lw["wqkv"].shape[1], cin=512, batch=B, a_bstride=0,
                      w_bstride=T * 512, bias=lw["bqkv"][1024:], bias_per_row=True, out_act=vt, ldo_a=Tp, oa_bstride=512 * Tp)
-            ops.attn_relpos_bf16(qk, qk[:, 512:], vt, p, lw["pu"], lw["pv"], ao, B=B, H=8, T=T, ldq=1024, ldk=1024, ldvt=Tp,
+            ops.attn_relpos_bf16(qk, qk[:, 512:], vt, pos, lw["pu"], lw["pv"], ao, B=B, H=8, T=T, ldq=1024, ldk=1024, ldvt=Tp,
                                  ldp=512, ldo=512, q_bs=T * 1024, k_bs=T * 1024, vt_bs=512 * Tp, o_bs=T * 512, scale=0.125,
                                  chunk=chunk, klen=klen)
-        elif self.split and getattr(self, "enc_attn", "mfma") == "mfma" and (klen is not None or keymask is None):
-            # split build: the same attention on the MFMA with every operand as bf16 hi + lo (mmx_attn_relpos_x; prefix masks
-            # only: the batched encoder's klen)
-            qkv = self._new(R, 1536)
-            ops.linear(hn, lw["wqkv"], 512, dtype=dt, bias=lw["bqkv"], out_act=qkv)
-            ops.attn_relpos_x(qkv, qkv[:, 512:], qkv[:, 1024:], p, lw["pu"], lw["pv"], ao, B=B, H=8, T=T, ldq=1536, ldk=1536, ldv=1536,
-                              ldp=512, ldo=512, q_bs=T * 1536, k_bs=T * 1536, v_bs=T * 1536, o_bs=T * 512, scale=0.125, chunk=chunk, klen=klen)
         else:
-            qkv = self._new(R, 1536)
-            ops.linear(hn, lw["wqkv"], 512, dtype=dt, bias=lw["bqkv"], out_act=qkv)
-            ops.attn_dense(qkv, qkv[:, 512:], qkv[:, 1024:], ao, B=B, H=8, Tq=T, Tk=T, ldq=1536, ldk=1536, ldv=1536, ldo=512,
-                           q_bs=T * 1536, k_bs=T * 1536, v_bs=T * 1536, o_bs=T * 512, scale=0.125, dtype=dt, chunk=chunk, pos=p,
-                           ldp=512, pos_u=lw["pu"], pos_v=lw["pv"], keymask=keymask)
+            if qkv is None:
+                qkv = self._new(R, 1536)
+            ops.linear(hn, lw["wqkv"], 512, dtype=dt, bias=lw["bqkv"], out_act=qkv[t0:])
+            if not dense:
+                ops.attn_relpos_x(qkv, qkv[:, 512:], qkv[:, 1024:], pos, lw["pu"], lw["pv"], ao, B=B, H=8, T=T, ldq=1536, ldk=1536,
+                                  ldv=1536, ldp=512, ldo=512, q_bs=T * 1536, k_bs=T * 1536, v_bs=T * 1536, o_bs=T * 512, scale=0.125,
+                                  chunk=chunk, klen=klen)
+            else:
+                ops.attn_dense(qkv, qkv[:, 512:], qkv[:, 1024:], ao, B=B, H=8, Tq=T, Tk=T, ldq=1536, ldk=1536, ldv=1536, ldo=512,
+                               q_bs=T * 1536, k_bs=T * 1536, v_bs=T * 1536, o_bs=T * 512, scale=0.125, dtype=dt, chunk=chunk, pos=pos,
+                               ldp=512, pos_u=lw["pu"], pos_v=lw["pv"], keymask=keymask, q_begin=t0)
         x2 = self._new(R, 512, f32=True)
-        ops.linear(ao, lw["wo"], 512, dtype=dt, bias=lw["bo"], residual=x, out_f32=x2)
+        ops.linear(ao[t0:], lw["wo"], 512, dtype=dt, bias=lw["bo"], residual=x, out_f32=x2)
         ops.rownorm(x2, lw["n2g"], lw["n2b"], 1e-12, rows=R, C_=512, out_act=hn, dtype=dt)
         ff = self._new(R, 2048)
         ops.linear(hn, lw["w1"], 512, dtype=dt, bias=lw["b1"], act="silu", out_act=ff)
@@ -374,49 +377,14 @@ class FlowEngine:
         """UpsampleConformerEncoder.forward (upsample_encoder.py:243-316) on embedded rows a0 [Lt, 512] (compute dtype);
         with finalize=False the last 3 rows are the look-ahead `context`.  Returns mu = encoder_proj(h) fp32 [2T, 80],
         or with hidden=True the encoder output h itself (after after_norm) as fp32 [2T, 512]."""
-        dt, E = self.dtype, self.enc
         Lt = a0.shape[0]
-        x_all, xa_all = self._embed(E["embed"], a0, Lt)
-        T = Lt if finalize else Lt - self.L
-        rows_in = Lt                                    # look-ahead context rows follow the T rows contiguously
-        # PreLookaheadLayer: conv k4 over [x ; context|zeros] -> leaky_relu(0.01) -> causal conv k3 -> + x
-        h1 = self._new(T, 512)
-        ops.gemm(xa_all, E["pl_w1"], T, 512, dtype=dt, lda=512, cin=512, ntaps=4, row_off=0, row_lo=0, row_hi=rows_in,
-                 bias=E["pl_b1"], act="lrelu", slope=0.01, out_act=h1, ldo_a=512)
-        x = self._new(T, 512, f32=True)
-        ops.conv1d(h1, E["pl_w2"], T=T, Cin=512, k=3, pad_left=2, dtype=dt, bias=E["pl_b2"], residual=x_all, out_f32=x)
-        pos = self._pos(T)
-        chunk = self.enc_chunk if streaming else 0
-        for lw in E["layers"]:
-            x = self._conformer(lw, x, T, pos, chunk)
-        # Upsample1D: nearest x2, left pad 4, conv k5
-        T2 = 2 * T
-        up = self._new(T2, 512)
-        ops.copy2d(x, F32, 0, 512, 1, up, dt, 0, 512, 1, rows=T2, cols=512, rep=2)
-        c5 = self._new(T2, 512)
-        ops.conv1d(up, E["up_w"], T=T2, Cin=512, k=5, pad_left=4, dtype=dt, bias=E["up_b"], out_act=c5)
-        x, _ = self._embed(E["up_embed"], c5, T2)
-        pos = self._pos(T2)
-        for lw in E["up_layers"]:
-            x = self._conformer(lw, x, T2, pos, 2 * chunk)
-        hn = self._new(T2, 512)
-        hf = self._new(T2, 512, f32=True) if hidden else None
-        ops.rownorm(x, E["ang"], E["anb"], 1e-5, rows=T2, C_=512, out_f32=hf, out_act=hn, dtype=dt)
-        if hidden:
-            return hf
-        mu = self._new(T2, 80, f32=True)
-        ops.linear(hn, E["wproj"], 512, dtype=dt, bias=E["bproj"], out_f32=mu)
-        return mu
+        return self._encode(a0, 1, Lt if finalize else Lt - self.L, self.enc_chunk if streaming else 0, hidden=hidden)[0]
 
     def encode_batch(self, ids_list) -> list:
         """UpsampleConformerEncoder.forward + encoder_proj for several whole utterances at once (finalize, no chunk masks):
         the token rows are zero padded to the longest, every launch covers the batch (the encoder is ~115 launches, most of
-        them too small to fill the chip one utterance at a time).  What makes the padding invisible to the valid rows:
-        the embedding output is masked to zero beyond each length (the look-ahead conv reads 3 rows to the right - zeros, as
-        at the end of a lone utterance), the other convs only look left, attention masks the keys beyond the length, and the
-        relative position of a (query, key) pair does not depend on the sequence length.  Returns mu fp32 [2 * L_b, 80] per
-        utterance (views of one buffer)."""
-        dt, E = self.dtype, self.enc
+        them too small to fill the chip one utterance at a time).  Returns mu fp32 [2 * L_b, 80] per utterance (views of
+        one buffer)."""
         B = len(ids_list)
         lens = [int(i.numel()) for i in ids_list]
         if B == 1:
@@ -425,38 +393,53 @@ class FlowEngine:
         ids = torch.zeros(B, T, dtype=torch.int64, device=self.dev)
         for b, i in enumerate(ids_list):
             ids[b, :lens[b]] = i.reshape(-1)
-        lens_t = torch.tensor(lens, dtype=torch.int32, device=self.dev)
-        ar = torch.arange(2 * T, device=self.dev)
-        mask = (ar[None, :T] < lens_t[:, None]).float().contiguous()             # [B, T]
-        mask2 = (ar[None, :] < 2 * lens_t[:, None]).float().contiguous()         # [B, 2T]
-        klen2 = (2 * lens_t).contiguous()
-        R = B * T
-        a0 = self._new(R, 512)
-        ops.gather_rows(ids.reshape(-1), self.emb_table, out_act=a0, dtype=dt)
-        x_all, xa_all = self._embed(E["embed"], a0, R, rowmask=mask.reshape(-1))
-        h1 = self._new(R, 512)
-        ops.gemm(xa_all, E["pl_w1"], T, 512, dtype=dt, lda=512, cin=512, ntaps=4, row_off=0, row_lo=0, row_hi=T, batch=B,
-                 a_bstride=T * 512, bias=E["pl_b1"], act="lrelu", slope=0.01, out_act=h1, ldo_a=512, oa_bstride=T * 512)
-        x = self._new(R, 512, f32=True)
+        a0 = self._new(B * T, 512)
+        ops.gather_rows(ids.reshape(-1), self.emb_table, out_act=a0, dtype=self.dtype)
+        mu = self._encode(a0, B, T, lens=torch.tensor(lens, dtype=torch.int32, device=self.dev))
+        return [mu[b, :2 * lens[b]] for b in range(B)]
+
+    def _encode(self, a0, B, T, chunk=0, lens=None, hidden=False):
+        """The encoder walk on B utterances of Lt embedded rows each, a0 [B * Lt, 512]: T rows go through the layers, rows
+        T .. Lt-1 are the look-ahead context (a single non-final utterance).  lens int32 [B] (a zero-padded batch, T = Lt):
+        what makes the padding invisible to the valid rows is that the embedding output is masked to zero beyond each length
+        (the look-ahead conv reads 3 rows to the right - zeros, as at the end of a lone utterance), the other convs only look
+        left, attention masks the keys beyond the length, and the relative position of a (query, key) pair does not depend on
+        the sequence length.  Returns mu fp32 [B, 2T, 80], or with hidden=True h (after after_norm) fp32 [B, 2T, 512]."""
+        dt, E = self.dtype, self.enc
+        Lt, T2 = a0.shape[0] // B, 2 * T
+        mask = mask2 = klen2 = None
+        if lens is not None:
+            ar = torch.arange(T2, device=self.dev)
+            mask = (ar[None, :T] < lens[:, None]).float().contiguous()             # [B, T]
+            mask2 = (ar[None, :] < 2 * lens[:, None]).float().contiguous()         # [B, 2T]
+            klen2 = (2 * lens).contiguous()
+        x_all, xa_all = self._embed(E["embed"], a0, B * Lt, rowmask=(None if mask is None else mask.reshape(-1)))
+        # PreLookaheadLayer: conv k4 over [x ; context|zeros] -> leaky_relu(0.01) -> causal conv k3 -> + x
+        h1 = self._new(B * T, 512)
+        ops.gemm(xa_all, E["pl_w1"], T, 512, dtype=dt, lda=512, cin=512, ntaps=4, row_off=0, row_lo=0, row_hi=Lt, batch=B,
+                 a_bstride=Lt * 512, bias=E["pl_b1"], act="lrelu", slope=0.01, out_act=h1, ldo_a=512, oa_bstride=T * 512)
+        x = self._new(B * T, 512, f32=True)
         ops.conv1d(h1, E["pl_w2"], T=T, Cin=512, k=3, pad_left=2, dtype=dt, batch=B, bias=E["pl_b2"], residual=x_all, out_f32=x)
-        pos = self._pos(T)
-        km, km2 = (None, None) if self.enc_mfma else (mask, mask2)
+        pe = self._pos(T)
         for lw in E["layers"]:
-            x = self._conformer(lw, x, T, pos, 0, B=B, klen=lens_t, keymask=km)
-        T2 = 2 * T
+            x = self._conformer(lw, x, T, chunk, pe, B=B, klen=lens, keymask=mask)
+        # Upsample1D: nearest x2, left pad 4, conv k5
         up = self._new(B * T2, 512)
         ops.copy2d(x, F32, T * 512, 512, 1, up, dt, T2 * 512, 512, 1, rows=T2, cols=512, batch=B, rep=2)
         c5 = self._new(B * T2, 512)
         ops.conv1d(up, E["up_w"], T=T2, Cin=512, k=5, pad_left=4, dtype=dt, batch=B, bias=E["up_b"], out_act=c5)
         x, _ = self._embed(E["up_embed"], c5, B * T2)
-        pos = self._pos(T2)
+        pe = self._pos(T2)
         for lw in E["up_layers"]:
-            x = self._conformer(lw, x, T2, pos, 0, B=B, klen=klen2, keymask=km2)
+            x = self._conformer(lw, x, T2, 2 * chunk, pe, B=B, klen=klen2, keymask=mask2)
         hn = self._new(B * T2, 512)
-        ops.rownorm(x, E["ang"], E["anb"], 1e-5, rows=B * T2, C_=512, out_act=hn, dtype=dt)
+        hf = self._new(B, T2, 512, f32=True) if hidden else None
+        ops.rownorm(x, E["ang"], E["anb"], 1e-5, rows=B * T2, C_=512, out_f32=hf, out_act=hn, dtype=dt)
+        if hidden:
+            return hf
         mu = self._new(B, T2, 80, f32=True)
         ops.linear(hn, E["wproj"], 512, dtype=dt, bias=E["bproj"], out_f32=mu)
-        return [mu[b, :2 * lens[b]] for b in range(B)]
+        return mu
 
     # ------------------------------------------------------------------ streaming encoder with cached state
     def _enc_stream_state(self, st):
@@ -483,27 +466,6 @@ class FlowEngine:
                           pos=pos_tables(E["layers"], Tt), pos2=pos_tables(E["up_layers"], Tf), Tt=Tt, Tf=Tf)
         return st.enc
 
-    def _conformer_stream(self, lw, x, t0, T, qkv, pos_all, Tcap, chunk):
-        """One ConformerEncoderLayer on rows t0 .. T-1 (x fp32 [T - t0, 512] window, returned likewise); qkv [Tcap, 1536]
-        holds the Q|K|V rows of ALL positions, pos_all [2*Tcap - 1, 512] the projected rel-pos table of the capacity."""
-        dt, n = self.dtype, T - t0
-        hn = self._new(n, 512)
-        ops.rownorm(x, lw["n1g"], lw["n1b"], 1e-12, rows=n, C_=512, out_act=hn, dtype=dt)
-        ops.linear(hn, lw["wqkv"], 512, dtype=dt, bias=lw["bqkv"], out_act=qkv[t0:T])
-        ao = self._new(T, 512)
-        # the kernel indexes pos[T - 1 - i + j]: shift the base so that this is row Tcap - 1 - (i - j) of the full table
-        ops.attn_dense(qkv, qkv[:, 512:], qkv[:, 1024:], ao, B=1, H=8, Tq=T, Tk=T, ldq=1536, ldk=1536, ldv=1536, ldo=512,
-                       q_bs=0, k_bs=0, v_bs=0, o_bs=0, scale=0.125, dtype=dt, chunk=chunk, pos=pos_all[Tcap - T:], ldp=512,
-                       pos_u=lw["pu"], pos_v=lw["pv"], q_begin=t0)
-        x2 = self._new(n, 512, f32=True)
-        ops.linear(ao[t0:T], lw["wo"], 512, dtype=dt, bias=lw["bo"], residual=x, out_f32=x2)
-        ops.rownorm(x2, lw["n2g"], lw["n2b"], 1e-12, rows=n, C_=512, out_act=hn, dtype=dt)
-        ff = self._new(n, 2048)
-        ops.linear(hn, lw["w1"], 512, dtype=dt, bias=lw["b1"], act="silu", out_act=ff)
-        x3 = self._new(n, 512, f32=True)
-        ops.linear(ff, lw["w2"], 2048, dtype=dt, bias=lw["b2"], residual=x2, out_f32=x3)
-        return x3
-
     def _encode_stream_rows(self, st, ids: torch.Tensor, tb: int, Lt: int):
         """Streaming, non-final encode of ids [Lt] (the last 3 are look-ahead context) given that tokens 0 .. tb-1 are
         already encoded in the state: only tokens tb .. Lt-4 run through the layers; mu of their frames lands in the
@@ -525,7 +487,7 @@ class FlowEngine:
         ops.gemm(S["h1"], E["pl_w2"], n, 512, dtype=dt, lda=512, cin=512, ntaps=3, row_off=tb - 2, row_lo=0, row_hi=T,
                  bias=E["pl_b2"], residual=S["x"][tb:T], ldr=512, out_f32=x, ldo_f=512)
         for lw, qkv, pos in zip(E["layers"], S["qkv"], S["pos"]):
-            x = self._conformer_stream(lw, x, tb, T, qkv, pos, S["Tt"], self.enc_chunk)
+            x = self._conformer(lw, x, T, self.enc_chunk, qkv=qkv, pos=pos[S["Tt"] - T:], t0=tb)
         # Upsample1D: nearest x2, causal conv k5 (left pad 4) on frames 2tb .. 2T-1
         f0, F = 2 * tb, 2 * T
         ops.copy2d(x, F32, 0, 512, 1, S["up"][f0:F], dt, 0, 512, 1, rows=F - f0, cols=512, rep=2)
@@ -534,7 +496,7 @@ class FlowEngine:
                  bias=E["up_b"], out_act=c5, ldo_a=512)
         x, _ = self._embed(E["up_embed"], c5, F - f0)
         for lw, qkv, pos in zip(E["up_layers"], S["qkv2"], S["pos2"]):
-            x = self._conformer_stream(lw, x, f0, F, qkv, pos, S["Tf"], 2 * self.enc_chunk)
+            x = self._conformer(lw, x, F, 2 * self.enc_chunk, qkv=qkv, pos=pos[S["Tf"] - F:], t0=f0)
         hn = self._new(F - f0, 512)
         ops.rownorm(x, E["ang"], E["anb"], 1e-5, rows=F - f0, C_=512, out_act=hn, dtype=dt)
         ops.linear(hn, E["wproj"], 512, dtype=dt, bias=E["bproj"], out_f32=S["mu"][f0:F])
@@ -563,30 +525,16 @@ class FlowEngine:
         hn = self._new(B, T, C)
         ops.rownorm(x, w["n1g"], w["n1b"], 1e-5, rows=T, C_=C, batch=B, out_act=hn, dtype=dt)
         ao = self._new(B, T, 512)
-        if dt == BF16:
-            qk = self._new(B, T, 1024)
-            ops.gemm(hn, w["wqk"], T, 1024, dtype=dt, lda=C, cin=C, batch=B, a_bstride=T * C, out_act=qk, ldo_a=1024,
-                     oa_bstride=T * 1024)
-            Tp = ops.round_up(T, 8)
-            vt = self._vt_buf(B, Tp)
+        qk, vt = self._attn_bufs(B, T, presplit=False)
+        ld = qk.shape[-1]
+        ops.gemm(hn, w["wqkv"] if vt is None else w["wqk"], T, ld, dtype=dt, lda=C, cin=C, batch=B, a_bstride=T * C, out_act=qk,
+                 ldo_a=ld, oa_bstride=T * ld)
+        if vt is not None:
             # V^T[b] = W_v (512x256) . X_b^T : A = weights, "W" operand = activations (batch stride on W)
             ops.gemm(w["wv"], hn, 512, T, dtype=dt, lda=w["wv"].shape[1], cin=C, batch=B, a_bstride=0, w_bstride=T * C,
-                     out_act=vt, ldo_a=Tp, oa_bstride=512 * Tp)
-            ops.attn_flash_bf16(qk, qk[:, :, 512:], vt, ao, B=B, H=8, T=T, ldq=1024, ldk=1024, ldvt=Tp, ldo=512,
-                                q_bs=T * 1024, k_bs=T * 1024, vt_bs=512 * Tp, o_bs=T * 512, scale=0.125, keymask=mask,
-                                chunk=chunk)
-        else:
-            qkv = self._new(B, T, 1536)
-            ops.gemm(hn, w["wqkv"], T, 1536, dtype=dt, lda=C, cin=C, batch=B, a_bstride=T * C, out_act=qkv, ldo_a=1536,
-                     oa_bstride=T * 1536)
-            if self.split:
-                ops.attn_flash_x(qkv, qkv[:, :, 512:], qkv[:, :, 1024:], ao, B=B, H=8, T=T, ldq=1536, ldk=1536, ldv=1536, ldo=512,
-                                 q_bs=T * 1536, k_bs=T * 1536, v_bs=T * 1536, o_bs=T * 512, scale=0.125,
-                                 keymask=(None if klen is not None else mask), chunk=chunk, klen=klen)
-            else:
-                ops.attn_dense(qkv, qkv[:, :, 512:], qkv[:, :, 1024:], ao, B=B, H=8, Tq=T, Tk=T, ldq=1536, ldk=1536, ldv=1536,
-                               ldo=512, q_bs=T * 1536, k_bs=T * 1536, v_bs=T * 1536, o_bs=T * 512, scale=0.125, dtype=dt,
-                               keymask=mask, chunk=chunk)
+                     out_act=vt, ldo_a=vt.shape[-1], oa_bstride=512 * vt.shape[-1])
+        # the bf16 build's per-op path reads the key mask, not the lengths
+        self._attention(qk, vt, ao, B=B, T=T, chunk=chunk, mask=mask, klen=(None if dt == BF16 else klen))
         ops.gemm(ao, w["wo"], T, C, dtype=dt, lda=512, cin=512, batch=B, a_bstride=T * 512, bias=w["bo"], residual=x,
                  ldr=C, r_bstride=T * C, out_f32=x, ldo_f=C, of_bstride=T * C)
         ops.rownorm(x, w["n3g"], w["n3b"], 1e-5, rows=T, C_=C, batch=B, out_act=hn, dtype=dt)
@@ -598,19 +546,52 @@ class FlowEngine:
                  rowmask=(mask if act_out is not None else None), rm_bstride=T,
                  out_act=act_out, ldo_a=act_ld, oa_bstride=T * act_ld)
 
-    def _vt_buf(self, B, Tp, planes=1):
-        key = (B, Tp, planes)                          # referenced by recorded graphs: never evicted (<= 15 MB each)
-        if key not in self._vt:
-            self._vt[key] = torch.zeros(B, planes * 512, Tp, dtype=torch.bfloat16 if planes > 1 else self.tdt, device=self.dev)   # pad columns stay zero
-        return self._vt[key]
+    def _attn_layout(self, presplit):
+        """The operands of the estimator's attention in this build: (Q|K row width, its dtype, V^T planes).  bf16: Q | K rows
+        and V^T, read by attn_flash_bf16.  Split build with presplit (the fused kernels of a whole-sequence solve): bf16
+        [hi Q | hi K | lo Q | lo K] rows and V^T hi / lo planes, split once by their producer, read by attn_flash_xs.
+        Otherwise fp32 Q | K | V rows, read by attn_flash_x (split build) or attn_dense (fp32 build)."""
+        if self.dtype == BF16:
+            return 1024, self.tdt, 1
+        if self.split and presplit:
+            return 2048, torch.bfloat16, 2
+        return 1536, self.tdt, 0
 
-    def estimator(self, x, x_bstride, mu, spks, cond, t, B, T, mask=None, streaming=False, out=None, x_mod=None, klen=None):
-        """All inputs fp32 time-major device tensors: x [x_mod,T,80] (batch b reads x[b % x_mod]), mu/cond [B,T,80],
-        spks [B,80], t [B]; mask fp32 [B,T] or None.  Returns fp32 [B,T,80]."""
-        if self.fused or (self.fused is None and (self.dtype == BF16 or self.split or B * ((T + 15) // 16) >= 256)):
-            return self._estimator_fused(x, x_bstride, mu, spks, cond, t, B, T, mask, streaming, out, x_mod, klen)
-        dt, C = self.dtype, self.C
-        chunk = self.est_chunk if streaming else 0
+    def _attn_bufs(self, B, T, presplit):
+        """Q|K rows [B, T, width] and V^T [B, planes * 512, round_up(T, 8)] (None without planes) of a whole-sequence call.
+        The V^T buffers are referenced by recorded graphs: never evicted (<= 15 MB each); their pad columns stay zero."""
+        ld, qdt, planes = self._attn_layout(presplit)
+        qk = torch.empty(B, T, ld, dtype=qdt, device=self.dev)
+        if not planes:
+            return qk, None
+        key = (B, ops.round_up(T, 8), planes)
+        if key not in self._vt:
+            self._vt[key] = torch.zeros(B, planes * 512, key[1], dtype=torch.bfloat16, device=self.dev)
+        return qk, self._vt[key]
+
+    def _attention(self, qk, vt, ao, *, B, T, chunk, mask=None, klen=None, q_begin=0, fp8=False, form=0):
+        """The estimator's attention on operands laid out by _attn_layout, by the kernel that reads that layout: qk [B, Tc,
+        width], vt [B, planes * 512, ldvt] or None, out ao [B, Tc, 512]; queries q_begin .. T-1.  klen (the prefix masks of
+        a padded group) replaces the key mask in the kernels that take it; fp8 (bf16) and form (split) select variants."""
+        ld, Tc = qk.shape[-1], qk.shape[1]
+        km = None if klen is not None else mask
+        kw = dict(B=B, H=8, ldo=512, o_bs=Tc * 512, scale=0.125, chunk=chunk, q_begin=q_begin)
+        if vt is None and not self.split:
+            ops.attn_dense(qk, qk[:, :, 512:], qk[:, :, 1024:], ao, Tq=T, Tk=T, ldq=ld, ldk=ld, ldv=ld, q_bs=Tc * ld, k_bs=Tc * ld,
+                           v_bs=Tc * ld, dtype=self.dtype, keymask=mask, **kw)
+        elif vt is None:
+            ops.attn_flash_x(qk, qk[:, :, 512:], qk[:, :, 1024:], ao, T=T, ldq=ld, ldk=ld, ldv=ld, q_bs=Tc * ld, k_bs=Tc * ld,
+                             v_bs=Tc * ld, keymask=km, klen=klen, **kw)
+        elif self.split:
+            ops.attn_flash_xs(qk, vt, ao, T=T, ldqk=ld, ldvt=vt.shape[-1], qk_bs=Tc * ld, vt_bs=vt[0].numel(), keymask=km,
+                              klen=klen, form=form, **kw)
+        else:
+            ops.attn_flash_bf16(qk, qk[:, :, 512:], vt, ao, T=T, ldq=ld, ldk=ld, ldvt=vt.shape[-1], q_bs=Tc * ld, k_bs=Tc * ld,
+                                vt_bs=vt[0].numel(), keymask=km, fp8=fp8, klen=klen, **kw)
+
+    def _time_mlp(self, t, B):
+        """Sinusoidal embedding of t [B], time MLP and mish, then all 14 ResNet blocks' MLPs in one GEMM: fp32 [B, 14 * 256]."""
+        dt = self.dtype
         te = self._new(B, self.tdim)
         ops.sinusoidal_emb(t, te, dim=self.tdim, dtype=dt)
         t1 = self._new(B, 1024)
@@ -618,44 +599,64 @@ class FlowEngine:
         t2 = self._new(B, 1024)
         ops.linear(t1, self.t_w2, 1024, dtype=dt, bias=self.t_b2, act2="mish", out_act=t2)       # mish(time_mlp(t))
         tv = self._new(B, self.mlp_w.shape[0], f32=True)
-        ops.linear(t2, self.mlp_w, 1024, dtype=dt, bias=self.mlp_b, out_f32=tv)                  # all 14 resnet mlps
-        h0 = self._new(B, T, 320)
-        ops.est_pack(x, mu, spks, cond, h0, B=B, T=T, dtype=dt, x_bstride=x_bstride, x_mod=(x_mod or B))
-        xs = self._new(B, T, C, f32=True)
-        cat = self._new(B, T, 2 * C)                     # [mid output | skip] for the up block
-        # down block: resnet + 4 transformer blocks; the last block drops its activation copy into cat[:, :, C:]
-        self._resnet(self.down["res"], h0, 320, B, T, tv, mask, xs)
-        for j, w in enumerate(self.down["blocks"]):
-            last = j == 3
-            self._tblock(w, xs, B, T, mask, chunk, act_out=(cat[:, :, C:] if last else None), act_ld=2 * C, klen=klen)
-        a = self._new(B, T, C)
-        ops.gemm(cat[:, :, C:], self.down_w, T, C, dtype=dt, lda=2 * C, cin=C, ntaps=3, row_off=-2, row_lo=0, row_hi=T,
-                 batch=B, a_bstride=T * 2 * C, bias=self.down_b, rowmask=mask, rm_bstride=T, out_act=a, ldo_a=C,
-                 oa_bstride=T * C)
-        lda = C
-        for i, st in enumerate(self.mid):
-            self._resnet(st["res"], a, lda, B, T, tv, mask, xs)
-            lastst = i == len(self.mid) - 1
-            for j, w in enumerate(st["blocks"]):
-                last = j == 3
-                if last and lastst:
-                    self._tblock(w, xs, B, T, mask, chunk, act_out=cat, act_ld=2 * C, klen=klen)
-                elif last:
-                    self._tblock(w, xs, B, T, mask, chunk, act_out=a, act_ld=C, klen=klen)
-                else:
-                    self._tblock(w, xs, B, T, mask, chunk, klen=klen)
-        self._resnet(self.up["res"], cat, 2 * C, B, T, tv, mask, xs)
-        for j, w in enumerate(self.up["blocks"]):
-            self._tblock(w, xs, B, T, mask, chunk, act_out=(a if j == 3 else None), act_ld=C, klen=klen)
-        a2 = self._new(B, T, C)
-        ops.conv1d(a, self.up_w, T=T, Cin=C, k=3, pad_left=2, dtype=dt, batch=B, bias=self.up_b, rowmask=mask, out_act=a2)
-        c1 = self._new(B, T, C, f32=True)
-        ops.conv1d(a2, self.fin_w, T=T, Cin=C, k=3, pad_left=2, dtype=dt, batch=B, bias=self.fin_b, out_f32=c1)
-        ops.rownorm(c1, self.fin_g, self.fin_be, 1e-5, rows=T, C_=C, batch=B, act="mish", rowmask=mask, out_act=a, dtype=dt)
-        if out is None:
-            out = self._new(B, T, 80, f32=True)
-        ops.conv1d(a, self.proj_w, T=T, Cin=C, k=1, dtype=dt, batch=B, bias=self.proj_b, rowmask=mask, out_f32=out)
-        return out
+        ops.linear(t2, self.mlp_w, 1024, dtype=dt, bias=self.mlp_b, out_f32=tv)
+        return tv
+
+    def estimator(self, x, x_bstride, mu, spks, cond, t, B, T, mask=None, streaming=False, out=None, x_mod=None, klen=None):
+        """All inputs fp32 time-major device tensors: x [x_mod,T,80] (batch b reads x[b % x_mod]), mu/cond [B,T,80],
+        spks [B,80], t [B]; mask fp32 [B,T] or None.  Returns fp32 [B,T,80]."""
+        C, chunk = self.C, (self.est_chunk if streaming else 0)
+        tv = self._time_mlp(t, B)
+        a = self._new(B, T, C)                           # the mid, up and final activations share one buffer
+        S = dict(h0=self._new(B, T, 320), cat=self._new(B, T, 2 * C), amid=[a] * len(self.mid), aup=a, a2=self._new(B, T, C),
+                 c1=self._new(B, T, C, f32=True), afin=a, d=(self._new(B, T, 80, f32=True) if out is None else out),
+                 xs=self._new(B, T, C, f32=True))
+        ops.est_pack(x, mu, spks, cond, S["h0"], B=B, T=T, dtype=self.dtype, x_bstride=x_bstride, x_mod=(x_mod or B))
+        if self.fused or (self.fused is None and (self.dtype == BF16 or self.split or B * ((T + 15) // 16) >= 256)):
+            S["ao"] = self._new(B, T, 512)
+            self._estimator_rows(S, tv, B, T, chunk, itertools.repeat(self._attn_bufs(B, T, presplit=True)), mask=mask,
+                                 klen=klen, fp8=self.attn_fp8, form=(self.polite_flash_form if self.polite else 0))
+            return S["d"]
+
+        def stage(sw, a_in, lda, act_out, act_ld):
+            self._resnet(sw["res"], a_in, lda, B, T, tv, mask, S["xs"])
+            for j, w in enumerate(sw["blocks"]):
+                last = j == len(sw["blocks"]) - 1
+                self._tblock(w, S["xs"], B, T, mask, chunk, act_out=(act_out if last else None), act_ld=act_ld, klen=klen)
+
+        self._walk(stage, S, B, T, mask)
+        return S["d"]
+
+    def _walk(self, stage, S, B, T, mask=None, r0=0, Tc=None):
+        """The estimator's U-Net from est_pack's rows S["h0"] to S["d"] fp32 [B, Tc, 80] over frames r0 .. T-1 of buffers
+        allocated for Tc (default T) frames: down stage, causal conv, mid stages, up stage on [last mid | skip], up conv,
+        final block, projection.  stage(sw, a_in, lda, act_out, act_ld) runs one stage's ResNet and transformer blocks on
+        a_in [B, Tc, lda] and writes the masked activation copy of its last block into act_out (row stride act_ld).
+        S: h0, cat [B, Tc, 2C] (the down stage's skip in its upper half), amid (each mid stage's input), aup, a2, c1 (fp32),
+        afin, d.  The convs read the frames before r0 as their halo; mask (whole sequences only) is the row mask."""
+        dt, C, Tc = self.dtype, self.C, Tc or T
+        assert mask is None or r0 == 0
+
+        def conv3(src, ld, w, b, rowmask, out_act=None, out_f32=None):
+            # causal conv k3, A addressed from frame 0 of the buffer (the kernel's buffer descriptor cannot reach below its
+            # base): output row m is frame r0 + m and reads frames r0 + m + tap - 2
+            N = w.shape[0]
+            ops.gemm(src, w, T - r0, N, dtype=dt, lda=ld, cin=C, ntaps=3, row_off=r0 - 2, row_lo=0, row_hi=T, batch=B,
+                     a_bstride=Tc * ld, bias=b, rowmask=rowmask, rm_bstride=Tc, out_act=(None if out_act is None else out_act[:, r0:]),
+                     ldo_a=N, oa_bstride=Tc * N, out_f32=(None if out_f32 is None else out_f32[:, r0:]), ldo_f=N, of_bstride=Tc * N)
+
+        stage(self.down, S["h0"], 320, S["cat"][:, :, C:], 2 * C)
+        conv3(S["cat"][:, :, C:], 2 * C, self.down_w, self.down_b, mask, out_act=S["amid"][0])
+        for i, sw in enumerate(self.mid):
+            last = i == len(self.mid) - 1
+            stage(sw, S["amid"][i], C, S["cat"] if last else S["amid"][i + 1], 2 * C if last else C)
+        stage(self.up, S["cat"], 2 * C, S["aup"], C)
+        conv3(S["aup"], C, self.up_w, self.up_b, mask, out_act=S["a2"])
+        conv3(S["a2"], C, self.fin_w, self.fin_b, None, out_f32=S["c1"])
+        ops.rownorm(S["c1"][:, r0:], self.fin_g, self.fin_be, 1e-5, rows=T - r0, C_=C, batch=B, x_bstride=Tc * C, act="mish",
+                    rowmask=mask, out_act=S["afin"][:, r0:], o_bstride=Tc * C, dtype=dt)
+        ops.gemm(S["afin"][:, r0:], self.proj_w, T - r0, 80, dtype=dt, lda=C, cin=C, row_hi=T - r0, batch=B, a_bstride=Tc * C,
+                 bias=self.proj_b, rowmask=mask, rm_bstride=Tc, out_f32=S["d"][:, r0:], ldo_f=80, of_bstride=Tc * 80)
 
     # ------------------------------------------------------------------ estimator on the row-tile fused kernels
     # measured time (us, bf16) of ONE launch of est_tail_kernel with few workgroups, by tile height (tools/tail_lab.py: 16 rows
@@ -688,7 +689,7 @@ class FlowEngine:
             return bm, bm
         if self.split:
             # two bf16 planes per LDS tile: the ResNet kernel's largest tile is 32 rows (the 512-channel ResNet of the up block:
-            # 16, see _estimator_fused); the tail kernel has a 64-row form (attention tile in K halves, 256-wide FF chunks) whose
+            # 16, see _estimator_rows); the tail kernel has a 64-row form (attention tile in K halves, 256-wide FF chunks) whose
             # MFMA stages run at the MFMA's rate instead of the weight stream's: the tile with the shortest launch, and 64 rows
             # (half the workgroups of the 32-row tile at 0.85 of its time per row) beside the decode loop
             cap = getattr(self, "max_tile_rows", 64)
@@ -699,86 +700,35 @@ class FlowEngine:
             return bm, br
         return (32 if tiles(32) >= 128 else 16), 16            # fp32: tail, resnet (LDS: fp32 tiles are twice as large)
 
-    def _estimator_fused(self, x, x_bstride, mu, spks, cond, t, B, T, mask, streaming, out, x_mod, klen=None):
-        dt, C = self.dtype, self.C
-        chunk = self.est_chunk if streaming else 0
-        bm_t, bm_r = self._tile_rows(B, T)
-        te = self._new(B, self.tdim)
-        ops.sinusoidal_emb(t, te, dim=self.tdim, dtype=dt)
-        t1 = self._new(B, 1024)
-        ops.linear(te, self.t_w1, self.tdim, dtype=dt, bias=self.t_b1, act="silu", out_act=t1)
-        t2 = self._new(B, 1024)
-        ops.linear(t1, self.t_w2, 1024, dtype=dt, bias=self.t_b2, act2="mish", out_act=t2)
-        ntv = self.mlp_w.shape[0]
-        tv = self._new(B, ntv, f32=True)
-        ops.linear(t2, self.mlp_w, 1024, dtype=dt, bias=self.mlp_b, out_f32=tv)
-        h0 = self._new(B, T, 320)
-        ops.est_pack(x, mu, spks, cond, h0, B=B, T=T, dtype=dt, x_bstride=x_bstride, x_mod=(x_mod or B))
-        xs = self._new(B, T, C, f32=True)
-        cat = self._new(B, T, 2 * C)
-        a = self._new(B, T, C)
-        ao = self._new(B, T, 512)
-        bf = dt == BF16
-        if bf:
-            Tp = ops.round_up(T, 8)
-            qk, vt = self._new(B, T, 1024), self._vt_buf(B, Tp)
-            vt_bs = 512 * Tp
-        elif self.split:
-            # the producer splits the attention operands once: bf16 [hi Q | hi K | lo Q | lo K] rows and V^T planes
-            Tp = ops.round_up(T, 8)
-            qk = torch.empty(B, T, 2048, dtype=torch.bfloat16, device=self.dev)
-            vt = self._vt_buf(B, Tp, planes=2)
-            vt_bs = 2 * 512 * Tp
-        else:
-            qk, vt, Tp, vt_bs = self._new(B, T, 1536), None, 0, 0
-        ldq = qk.shape[-1]
+    def _estimator_rows(self, S, tv, B, T, chunk, attn_bufs, mask=None, klen=None, r0=0, Tc=None, fp8=False, form=0):
+        """The estimator's walk on the fused row-tile kernels (csrc/fused.hip: est_resnet, then attention + est_tail per
+        transformer block, each also producing the next block's Q|K(|V) rows) over frames r0 .. T-1 of buffers allocated for
+        Tc (default T) frames: a whole sequence (estimator) or a streaming hop (_cfm_stream_rows).  S: the buffers of _walk
+        plus xs fp32 [B, Tc, 256] (the residual stream) and ao [B, Tc, 512]; tv: _time_mlp.  attn_bufs yields the (Q|K rows,
+        V^T) pair of each transformer block in walk order: one shared pair for a whole sequence, a cached pair per block in a
+        streaming state.  mask / klen: row mask and key lengths of a padded group; fp8 / form: see _attention."""
+        dt, C, Tc = self.dtype, self.C, Tc or T
+        bm_t, bm_r = self._tile_rows(B, T - r0)
+        ntv = tv.shape[1]
 
-        def nxt(w):
-            return ops.est_next(wqkv=w["wqkv_p"], n1g=w["n1g"], n1b=w["n1b"], q_out=qk, ldq=ldq, q_bs=T * ldq, vt_out=vt, ldvt=Tp,
-                                vt_bs=vt_bs)
+        def nxt(w, qk, vt):
+            return ops.est_next(wqkv=w["wqkv_p"], n1g=w["n1g"], n1b=w["n1b"], q_out=qk, ldq=qk.shape[-1], q_bs=Tc * qk.shape[-1],
+                                vt_out=vt, ldvt=(0 if vt is None else vt.shape[-1]), vt_bs=(0 if vt is None else vt[0].numel()))
 
-        def attention():
-            if bf:
-                ops.attn_flash_bf16(qk, qk[:, :, 512:], vt, ao, B=B, H=8, T=T, ldq=1024, ldk=1024, ldvt=Tp, ldo=512, q_bs=T * 1024,
-                                    k_bs=T * 1024, vt_bs=512 * Tp, o_bs=T * 512, scale=0.125,
-                                    keymask=(None if klen is not None else mask), chunk=chunk, fp8=self.attn_fp8, klen=klen)
-            elif self.split:
-                ops.attn_flash_xs(qk, vt, ao, B=B, H=8, T=T, ldqk=2048, ldvt=Tp, ldo=512, qk_bs=T * 2048, vt_bs=vt_bs, o_bs=T * 512,
-                                  scale=0.125, keymask=(None if klen is not None else mask), chunk=chunk, klen=klen,
-                                  form=(self.polite_flash_form if self.polite else 0))
-            else:
-                ops.attn_dense(qk, qk[:, :, 512:], qk[:, :, 1024:], ao, B=B, H=8, Tq=T, Tk=T, ldq=1536, ldk=1536, ldv=1536, ldo=512,
-                               q_bs=T * 1536, k_bs=T * 1536, v_bs=T * 1536, o_bs=T * 512, scale=0.125, dtype=dt, keymask=mask,
-                               chunk=chunk)
-
-        def stage(st, a_in, lda, cin, act_out, act_ld):
-            r, blocks = st["res"], st["blocks"]
-            ops.est_resnet(a_in, lda, cin, xs, r, tv[:, r["idx"] * C:], ntv, B=B, T=T, dtype=dt,
-                           bm=(16 if (self.split and cin > 320) else bm_r), rowmask=mask, nxt=nxt(blocks[0]))
+        def stage(sw, a_in, lda, act_out, act_ld):
+            r, blocks = sw["res"], sw["blocks"]
+            bufs = [next(attn_bufs) for _ in blocks]
+            ops.est_resnet(a_in, lda, lda, S["xs"], r, tv[:, r["idx"] * C:], ntv, B=B, T=T, dtype=dt,
+                           bm=(16 if (self.split and lda > 320) else bm_r), rowmask=mask, nxt=nxt(blocks[0], *bufs[0]),
+                           t_begin=r0, Tcap=Tc)
             for j, w in enumerate(blocks):
-                attention()
                 last = j == len(blocks) - 1
-                ops.est_tail(ao, xs, w, B=B, T=T, dtype=dt, bm=bm_t, rowmask=(mask if last else None),
-                             act_out=(act_out if last else None), act_ld=act_ld, nxt=(None if last else nxt(blocks[j + 1])))
+                self._attention(*bufs[j], S["ao"], B=B, T=T, chunk=chunk, mask=mask, klen=klen, q_begin=r0, fp8=fp8, form=form)
+                ops.est_tail(S["ao"], S["xs"], w, B=B, T=T, dtype=dt, bm=bm_t, rowmask=(mask if last else None),
+                             act_out=(act_out if last else None), act_ld=act_ld,
+                             nxt=(None if last else nxt(blocks[j + 1], *bufs[j + 1])), t_begin=r0, Tcap=Tc)
 
-        # down block: its last transformer block drops the masked activation copy into cat[:, :, C:] (the skip)
-        stage(self.down, h0, 320, 320, cat[:, :, C:], 2 * C)
-        ops.gemm(cat[:, :, C:], self.down_w, T, C, dtype=dt, lda=2 * C, cin=C, ntaps=3, row_off=-2, row_lo=0, row_hi=T,
-                 batch=B, a_bstride=T * 2 * C, bias=self.down_b, rowmask=mask, rm_bstride=T, out_act=a, ldo_a=C,
-                 oa_bstride=T * C)
-        for i, st in enumerate(self.mid):
-            lastst = i == len(self.mid) - 1
-            stage(st, a, C, C, cat if lastst else a, 2 * C if lastst else C)
-        stage(self.up, cat, 2 * C, 2 * C, a, C)
-        a2 = self._new(B, T, C)
-        ops.conv1d(a, self.up_w, T=T, Cin=C, k=3, pad_left=2, dtype=dt, batch=B, bias=self.up_b, rowmask=mask, out_act=a2)
-        c1 = self._new(B, T, C, f32=True)
-        ops.conv1d(a2, self.fin_w, T=T, Cin=C, k=3, pad_left=2, dtype=dt, batch=B, bias=self.fin_b, out_f32=c1)
-        ops.rownorm(c1, self.fin_g, self.fin_be, 1e-5, rows=T, C_=C, batch=B, act="mish", rowmask=mask, out_act=a, dtype=dt)
-        if out is None:
-            out = self._new(B, T, 80, f32=True)
-        ops.conv1d(a, self.proj_w, T=T, Cin=C, k=1, dtype=dt, batch=B, bias=self.proj_b, rowmask=mask, out_f32=out)
-        return out
+        self._walk(stage, S, B, T, mask, r0, Tc)
 
     # ------------------------------------------------------------------ streaming with cached state (BASELINE config 5)
     class StreamState:
@@ -832,14 +782,16 @@ class FlowEngine:
             self.T = self.tok_done = 0
 
         def step_buffers(self, s):
+            """Euler step s's buffers of FlowEngine._estimator_rows (the frame-indexed ones shared by all steps included)"""
             if self.steps[s] is None:
                 e, Tc = self.eng, self.Tcap
-                z = lambda *sh: torch.zeros(*sh, dtype=e.tdt, device=e.dev)
+                z = lambda *sh, dtype=e.tdt: torch.zeros(*sh, dtype=dtype, device=e.dev)
                 nblk = 4 * (2 + len(e.mid))
-                ldq = 1024 if e.dtype == BF16 else 1536
+                ldq, qdt, planes = e._attn_layout(presplit=False)
                 self.steps[s] = dict(h0=z(2, Tc, 320), amid=[z(2, Tc, e.C) for _ in e.mid], cat=z(2, Tc, 2 * e.C), aup=z(2, Tc, e.C),
-                                     a2=z(2, Tc, e.C), qk=[z(2, Tc, ldq) for _ in range(nblk)],
-                                     vt=([z(2, 512, Tc) for _ in range(nblk)] if e.dtype == BF16 else [None] * nblk))
+                                     a2=z(2, Tc, e.C), qk=[z(2, Tc, ldq, dtype=qdt) for _ in range(nblk)],
+                                     vt=[z(2, planes * 512, Tc, dtype=torch.bfloat16) if planes else None for _ in range(nblk)],
+                                     xs=self.xs, ao=self.ao, c1=self.c1, afin=self.afin, d=self.d)
             return self.steps[s]
 
     # streaming state pool: capacities are bucketed coarsely (multiples of 512 frames, at most stream_cap_frames: beyond
@@ -889,87 +841,10 @@ class FlowEngine:
                 total -= self._stream_state_bytes(pool[key].Tcap)
                 pool.pop(key).release()
 
-    def _estimator_stream(self, st, s, x_new, mu_new, spks2, cond_new, tb, T):
-        """One estimator call of Euler step s on frames tb .. T-1 of a streaming utterance (CFG pair, B = 2), reading the
-        cached rows of earlier hops.  x_new [1, n, 80], mu_new / cond_new [2, n, 80] (row 1 zero), spks2 [2, 80].
-        Returns d fp32 [2, Tcap, 80] (valid rows tb .. T-1)."""
-        dt, C, Tc = self.dtype, self.C, st.Tcap
-        S = st.step_buffers(s)
-        B, n = 2, T - tb
-        r0 = tb // 16 * 16                                   # tiles start on a 16-frame boundary: <= 15 finished frames are
-        chunk = self.est_chunk                               # recomputed (same inputs, same values)
-        bm_t, bm_r = self._tile_rows(B, T - r0)
-        te = self._new(B, self.tdim)
-        ops.sinusoidal_emb(st.t_all[s], te, dim=self.tdim, dtype=dt)
-        t1 = self._new(B, 1024)
-        ops.linear(te, self.t_w1, self.tdim, dtype=dt, bias=self.t_b1, act="silu", out_act=t1)
-        t2 = self._new(B, 1024)
-        ops.linear(t1, self.t_w2, 1024, dtype=dt, bias=self.t_b2, act2="mish", out_act=t2)
-        ntv = self.mlp_w.shape[0]
-        tv = self._new(B, ntv, f32=True)
-        ops.linear(t2, self.mlp_w, 1024, dtype=dt, bias=self.mlp_b, out_f32=tv)
-        h0w = self._new(B, n, 320)
-        ops.est_pack(x_new, mu_new, spks2, cond_new, h0w, B=B, T=n, dtype=dt, x_bstride=n * 80, x_mod=1)
-        S["h0"][:, tb:T].copy_(h0w)
-        bf = dt == BF16
-        blk = [0]
-
-        def nxt(w, i):
-            qk, vt = S["qk"][i], S["vt"][i]
-            return ops.est_next(wqkv=w["wqkv_p"], n1g=w["n1g"], n1b=w["n1b"], q_out=qk, ldq=qk.shape[-1], q_bs=Tc * qk.shape[-1],
-                                vt_out=vt, ldvt=(Tc if bf else 0), vt_bs=512 * Tc)
-
-        def attention(i):
-            qk, vt = S["qk"][i], S["vt"][i]
-            if bf:
-                ops.attn_flash_bf16(qk, qk[:, :, 512:], vt, st.ao, B=B, H=8, T=T, ldq=1024, ldk=1024, ldvt=Tc, ldo=512, q_bs=Tc * 1024,
-                                    k_bs=Tc * 1024, vt_bs=512 * Tc, o_bs=Tc * 512, scale=0.125, chunk=chunk, q_begin=r0)
-            elif self.split:
-                ops.attn_flash_x(qk, qk[:, :, 512:], qk[:, :, 1024:], st.ao, B=B, H=8, T=T, ldq=1536, ldk=1536, ldv=1536, ldo=512,
-                                 q_bs=Tc * 1536, k_bs=Tc * 1536, v_bs=Tc * 1536, o_bs=Tc * 512, scale=0.125, chunk=chunk, q_begin=r0)
-            else:
-                ops.attn_dense(qk, qk[:, :, 512:], qk[:, :, 1024:], st.ao, B=B, H=8, Tq=T, Tk=T, ldq=1536, ldk=1536, ldv=1536, ldo=512,
-                               q_bs=Tc * 1536, k_bs=Tc * 1536, v_bs=Tc * 1536, o_bs=Tc * 512, scale=0.125, dtype=dt, chunk=chunk,
-                               q_begin=r0)
-
-        def stage(sw, a_in, lda, cin, act_out, act_ld):
-            r, blocks = sw["res"], sw["blocks"]
-            i0 = blk[0]
-            ops.est_resnet(a_in, lda, cin, st.xs, r, tv[:, r["idx"] * C:], ntv, B=B, T=T, dtype=dt,
-                           bm=(16 if (self.split and cin > 320) else bm_r), nxt=nxt(blocks[0], i0), t_begin=r0, Tcap=Tc)
-            for j, w in enumerate(blocks):
-                attention(i0 + j)
-                last = j == len(blocks) - 1
-                ops.est_tail(st.ao, st.xs, w, B=B, T=T, dtype=dt, bm=bm_t, act_out=(act_out if last else None), act_ld=act_ld,
-                             nxt=(None if last else nxt(blocks[j + 1], i0 + j + 1)), t_begin=r0, Tcap=Tc)
-            blk[0] += len(blocks)
-
-        def conv3(src, ld, col0, cin, wgt, bias, out_act=None, out_f32=None, ldo=None):
-            """causal conv k3 over frames r0 .. T-1 of a cached [2, Tcap, ld] buffer (rows before r0 are the halo)"""
-            N = wgt.shape[0]
-            # A is addressed from frame 0 of the buffer (the kernel's buffer descriptor cannot reach below its base):
-            # output row m is frame r0 + m and reads frames r0 + m + tap - 2
-            ops.gemm(src[:, :, col0:], wgt, T - r0, N, dtype=dt, lda=ld, cin=cin, ntaps=3, row_off=r0 - 2, row_lo=0, row_hi=T,
-                     batch=B, a_bstride=Tc * ld, bias=bias, out_act=(out_act[:, r0:] if out_act is not None else None), ldo_a=N,
-                     oa_bstride=Tc * N, out_f32=(out_f32[:, r0:] if out_f32 is not None else None), ldo_f=N, of_bstride=Tc * N)
-
-        stage(self.down, S["h0"], 320, 320, S["cat"][:, :, C:], 2 * C)
-        conv3(S["cat"], 2 * C, C, C, self.down_w, self.down_b, out_act=S["amid"][0])
-        for i, sw in enumerate(self.mid):
-            lastst = i == len(self.mid) - 1
-            stage(sw, S["amid"][i], C, C, S["cat"] if lastst else S["amid"][i + 1], 2 * C if lastst else C)
-        stage(self.up, S["cat"], 2 * C, 2 * C, S["aup"], C)
-        conv3(S["aup"], C, 0, C, self.up_w, self.up_b, out_act=S["a2"])
-        conv3(S["a2"], C, 0, C, self.fin_w, self.fin_b, out_f32=st.c1)
-        ops.rownorm(st.c1[:, r0:], self.fin_g, self.fin_be, 1e-5, rows=T - r0, C_=C, batch=B, x_bstride=Tc * C, act="mish",
-                    out_act=st.afin[:, r0:], o_bstride=Tc * C, dtype=dt)
-        ops.gemm(st.afin[:, r0:], self.proj_w, T - r0, 80, dtype=dt, lda=C, cin=C, batch=B, a_bstride=Tc * C, bias=self.proj_b,
-                 out_f32=st.d[:, r0:], ldo_f=80, of_bstride=Tc * 80)
-        return st.d
-
     def _cfm_stream_rows(self, st, tb: int, T: int):
         """Euler-solves frames tb .. T-1 (whole 50-frame chunks) from the state's mu / speaker rows; the latents land in
-        st.lat.  Pure device work on state buffers (recorded into the per-hop hipGraph)."""
+        st.lat.  Each Euler step is one estimator call on the CFG pair (B = 2) over the step's buffers, reading the cached
+        rows of earlier hops.  Pure device work on state buffers (recorded into the per-hop hipGraph)."""
         assert tb < T <= st.Tcap and tb % self.est_chunk == 0 and T % self.est_chunk == 0, (tb, T, st.Tcap)
         n = T - tb
         W = st.window(n)
@@ -977,8 +852,14 @@ class FlowEngine:
         W["mu2"][0].copy_(st.enc["mu"][tb:T])
         W["cond2"][0].copy_(st.cond[tb:T])
         for s in range(self.n_timesteps):
-            d = self._estimator_stream(st, s, W["x"], W["mu2"], st.spks2, W["cond2"], tb, T)
-            ops.cfg_euler(W["x"], d[0, tb:T], d[1, tb:T], self.cfg, st.dt[s], n * 80)
+            S = st.step_buffers(s)
+            tv = self._time_mlp(st.t_all[s], 2)
+            h0w = self._new(2, n, 320)
+            ops.est_pack(W["x"], W["mu2"], st.spks2, W["cond2"], h0w, B=2, T=n, dtype=self.dtype, x_bstride=n * 80, x_mod=1)
+            S["h0"][:, tb:T].copy_(h0w)
+            # tiles start on a 16-frame boundary: <= 15 finished frames are recomputed (same inputs, same values)
+            self._estimator_rows(S, tv, 2, T, self.est_chunk, zip(S["qk"], S["vt"]), r0=tb // 16 * 16, Tc=st.Tcap)
+            ops.cfg_euler(W["x"], S["d"][0, tb:T], S["d"][1, tb:T], self.cfg, st.dt[s], n * 80)
         st.lat[tb:T].copy_(W["x"][0])
 
     @torch.no_grad()
