@@ -7,6 +7,11 @@ RCCL all-gather of the generated audio.  Inputs are resident on the device befor
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: setup (weights, engine, the two build passes), --warmup steps, the
+--steps timed steps, --dump-outputs, the JSON line.  --full adds, on one GPU, everything else the line can carry, measured
+after the timed region: the live rooflines, the extra workloads, the other fast build and the CPU baseline (--no-roofline /
+--no-extras / --no-cpu-baseline leave parts of it out).
 """
 import argparse
 import gc
@@ -372,12 +377,15 @@ def main():
     ap.add_argument("--checkpoint", default="bf16", choices=["bf16", "fp32"],
                     help="kind of the synthetic checkpoint (mmx/synth.py): bf16 = bf16-representable weights; fp32 = general fp32 weights and "
                          "trained-like weight norms, what the reference's loaders hand over - the split build then carries weight planes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the live kernel measurements after the timed region (profiler passes over the step itself)")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: after the timed region also measure the live rooflines, the extra workloads and builds and the CPU "
+                         "baseline; without it the line carries the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the live kernel measurements after the timed region (profiler passes over the step itself)")
     ap.add_argument("--flow-bm-min", type=int, default=0, help="tuning: smallest tile height of the fused flow kernels")
     ap.add_argument("--flow-bm", type=int, default=0, help="cap the fused flow kernels' tile height (tuning: 32 leaves registers for co-resident decode waves)")
     ap.add_argument("--attn", default="bf16", choices=["bf16", "fp8"], help="fp8: estimator attention on the fp8 MFMA (config 5)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single-utterance and fp32-build extra measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra workloads and the other fast build")
     ap.add_argument("--workload", default="batch", choices=["batch", "single", "longform"])
     ap.add_argument("--per-gpu", type=int, default=32)
     ap.add_argument("--flow-group", default="8", help="utterances per batched flow ODE solve (a list gives a ramp: k-th group)")
@@ -609,12 +617,12 @@ def main():
                 r["roofline_attn"] = measure_attn_kernel(e, log, nsteps)
             return r
 
-        if world == 1 and not a.no_roofline:
+        if world == 1 and a.full and not a.no_roofline:
             # `roofline`: the LM decode step as a whole - its projection family is the largest share of the step's GPU time
             # (profiles/r04_bench*_kernel_stats.csv) and the decode loop is the step's critical path; the other objects are the
             # largest single projection (roofline_lm) and the two flow kernels (roofline_flow / _attn)
             out.update(rooflines(eng, dt, shape_log, a.steps))
-        if world == 1:
+        if world == 1 and a.full:
             if a.workload == "batch" and not a.no_extras:
                 # extra keys, measured after the timed region
                 from mmx.pipeline import TtsEngine

@@ -19,8 +19,8 @@ pmc() {         # name, counters, filter words, command...
     rm -rf $out/pmc_$name
     echo "pmc $name done" >> $out/progress.log
 }
-kstats bench python3 bench.py --steps 5 --warmup 2 --no-extras &&
-kstats longform python3 bench.py --workload longform --steps 2 --warmup 1 --no-cpu-baseline --no-extras &&
+kstats bench python3 bench.py --steps 5 --warmup 2 --full --no-extras &&
+kstats longform python3 bench.py --workload longform --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras &&
 kstats cfm8x896 python3 tools/prof_cfm.py 8 896 &&
 kstats cfm3x992 python3 tools/prof_cfm.py 3 992 &&
 kstats cfm1x992 python3 tools/prof_cfm.py 1 992 &&

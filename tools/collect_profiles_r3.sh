@@ -24,8 +24,8 @@ pmc() {         # name, counters, filter words, command...
     echo "pmc $name done" >> $out/progress.log
 }
 if [ "$2" != "pmc" ]; then
-kstats bench python3 bench.py --steps 5 --warmup 2 --no-extras --no-cpu-baseline &&
-kstats bench_x python3 bench.py --dtype x --steps 3 --warmup 1 --no-extras --no-cpu-baseline &&
+kstats bench python3 bench.py --steps 5 --warmup 2 --full --no-extras --no-cpu-baseline &&
+kstats bench_x python3 bench.py --dtype x --steps 3 --warmup 1 --full --no-extras --no-cpu-baseline &&
 kstats decode_bf16 python3 tools/decode_alone.py --dtype bf16 --steps 2 &&
 kstats decode_x python3 tools/decode_alone.py --dtype x --steps 2 &&
 kstats cfm8x896 python3 tools/prof_cfm.py 8 896 bf16 &&

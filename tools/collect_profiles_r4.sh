@@ -24,9 +24,9 @@ pmc() {         # name, counters, filter words, command...
     echo "pmc $name done" >> $out/progress.log
 }
 if [ "$what" != "pmc" ]; then
-kstats bench_x python3 bench.py --steps 5 --warmup 2 --no-extras --no-cpu-baseline &&
-kstats bench_bf16 python3 bench.py --dtype bf16 --steps 5 --warmup 2 --no-extras --no-cpu-baseline &&
-kstats bench_x_fp32ckpt python3 bench.py --checkpoint fp32 --steps 3 --warmup 1 --no-extras --no-cpu-baseline &&
+kstats bench_x python3 bench.py --steps 5 --warmup 2 --full --no-extras --no-cpu-baseline &&
+kstats bench_bf16 python3 bench.py --dtype bf16 --steps 5 --warmup 2 --full --no-extras --no-cpu-baseline &&
+kstats bench_x_fp32ckpt python3 bench.py --checkpoint fp32 --steps 3 --warmup 1 --full --no-extras --no-cpu-baseline &&
 kstats decode_x python3 tools/decode_alone.py --dtype x --steps 2 &&
 kstats decode_bf16 python3 tools/decode_alone.py --dtype bf16 --steps 2 &&
 kstats cfm8x896_x python3 tools/prof_cfm.py 8 896 x &&

@@ -20,9 +20,9 @@ pmc() {         # name, counters, filter words, command...
     rm -rf $out/pmc_$name
     echo "pmc $name done" >> $out/progress.log
 }
-kstats bench_x python3 bench.py --steps 5 --warmup 2 --no-extras --no-cpu-baseline &&
-kstats bench_bf16 python3 bench.py --dtype bf16 --steps 5 --warmup 2 --no-extras --no-cpu-baseline &&
-kstats bench_x_fp32ckpt python3 bench.py --checkpoint fp32 --steps 3 --warmup 1 --no-extras --no-cpu-baseline &&
+kstats bench_x python3 bench.py --steps 5 --warmup 2 --full --no-extras --no-cpu-baseline &&
+kstats bench_bf16 python3 bench.py --dtype bf16 --steps 5 --warmup 2 --full --no-extras --no-cpu-baseline &&
+kstats bench_x_fp32ckpt python3 bench.py --checkpoint fp32 --steps 3 --warmup 1 --full --no-extras --no-cpu-baseline &&
 kstats decode_x python3 tools/decode_alone.py --dtype x --steps 2 &&
 kstats cfm8x896_x python3 tools/prof_cfm.py 8 896 x || exit 1
 for c in "FETCH_SIZE" "WRITE_SIZE"; do
