@@ -342,11 +342,29 @@ int mmx_swiglu(const float* gu, int64_t ldgu, int rows, int I, void* out, int64_
  * EOS (== eos_id) sets finished; ids > eos_id leave next_x unchanged (llm.py:755-756).
  * Every call advances state.step and state.pos (+1) of unfinished sequences.
  * forced != NULL: teacher forcing, forced[b*max_out + step] replaces the accepted token (the sampled id is
- * still recorded in sampled[b][step]).  logp_out (optional) receives log_softmax(logits). */
+ * still recorded in sampled[b][step]).  logp_out (optional) receives log_softmax(logits).
+ * error (field 7): 0 none; 1 = 100 EOS re-draws under ignore_eos still gave EOS (llm.py:271-273 raises there; the id is accepted);
+ *   2 = the sequence's column of the sampler table is out of range (mmx_sample_step_tab only, see below). */
 int mmx_sample_step(const float* logits, int64_t ldl, int V, int B, int eos_id, int top_k, float top_p,
                     int win_size, float tau_r, uint64_t seed, int32_t* state, int32_t* out_tokens, int max_out,
                     int32_t* sampled, const int32_t* forced, const float* speech_emb, int E, float* next_x,
                     int64_t ldx, float* logp_out, hipStream_t stream);
+/* The same step with the sampler's parameters PER SEQUENCE in device memory instead of launch scalars, so that a recorded decode
+ * step holds none of them (a new seed or nucleus width needs no new hipGraph) and every request of a batch has its own:
+ *   samp[field * B + b] (int32, field-major like `state`), fields
+ *     {0 mode, 1 top_k, 2 win_size, 3 top_p (fp32 bits), 4 tau_r (fp32 bits), 5 seed low word, 6 seed high word, 7 reserved = 0}
+ *   mode 0: ras_sampling (common.py:111-116) = what mmx_sample_step does;
+ *   mode 1: nucleus_sampling alone (common.py:119-134): the candidate prefix and the draw from noise stream which = 0, no
+ *           repetition window (win_size and tau_r are range-checked but unused);
+ *   mode 2: random_sampling alone (common.py:137-139): the full-vocabulary draw from noise stream which = 1 (top_p unused).
+ *   In every mode the EOS re-draw loop of llm.py:259-274 advances the trial index as in mode 0, and the noise is
+ *   oracle/philox.py exp_noise(seed, seq_id, step, trial, which, .).
+ * The kernel range-checks each column (the host cannot: the values are in device memory): mode outside 0..2, top_k outside 1..64 or
+ * win_size outside 0..64 sets state.error = 2 and state.finished = 1 for THAT sequence and draws nothing (out_tokens, sampled and
+ * next_x rows untouched); the other sequences of the launch are not affected.  Every other argument as for mmx_sample_step. */
+int mmx_sample_step_tab(const float* logits, int64_t ldl, int V, int B, int eos_id, const int32_t* samp, int32_t* state,
+                        int32_t* out_tokens, int max_out, int32_t* sampled, const int32_t* forced, const float* speech_emb,
+                        int E, float* next_x, int64_t ldx, float* logp_out, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Row-tile fused kernels of the CFM estimator (csrc/fused.hip).  One workgroup takes a tile of `bm` frames of one

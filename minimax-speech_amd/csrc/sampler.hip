@@ -81,7 +81,10 @@ constexpr int SAMP_WAVES = SAMP_THREADS / 64;
 constexpr int SAMP_MAXV = 13;        // V <= 6656 (speech_token_size + 3 = 6564)
 constexpr int SAMP_MAXK = 64;
 constexpr int SAMP_GROUPS = SAMP_THREADS / 8;   // 64 group maxima
-constexpr int SAMP_LIST = 512;       // candidates >= the top_k-th group maximum (ties / clustered values included)
+// candidates >= the top_k-th group maximum (ties / clustered values included).  With top_k = 64 the threshold is the SMALLEST group
+// maximum: covering all 64 groups takes ~300 of the largest elements on average and more than 512 in ~2 % of random inputs (coupon
+// collector), more than 2048 in ~1e-12
+constexpr int SAMP_LIST = 2048;
 
 // (value, index) of the better of two candidates across lanes with a DPP control (see common.h dpp_f32)
 template <int CTRL>
@@ -92,9 +95,23 @@ __device__ __forceinline__ ArgMax dpp_better(ArgMax a) {
     return better(a, o);
 }
 
-__global__ __launch_bounds__(SAMP_THREADS) void sample_step_kernel(
-    const float* __restrict__ logits, long ldl, int V, int eos_id, int top_k, float top_p, int win_size, float tau_r,
-    unsigned long long seed, int32_t* __restrict__ state, int32_t* __restrict__ out_tokens, int max_out,
+// The sampler's parameters of one sequence: launch scalars (mmx_sample_step) or one column of the device table `samp`
+// (mmx_sample_step_tab, include/mmx_hip.h), read at the top of the kernel beside the loop state.
+struct SampParams {
+    int mode, top_k, win_size;      // mode: 0 RAS, 1 nucleus only, 2 random only
+    float top_p, tau_r;
+    unsigned long long seed;
+};
+struct SampState { int pos, step, n_out, finished, min_len, max_len, seq; };     // fields 0..6 of `state`, read by the entry kernel
+constexpr int SAMP_RAS = 0, SAMP_NUCLEUS = 1, SAMP_RANDOM = 2;
+constexpr int SAMP_ERR_TRIALS = 1, SAMP_ERR_PARAMS = 2;     // state field 7
+
+// MODES = false: the scalar entry point (RAS only, parameters checked on the host); true: the table entry point (the column's
+// mode and ranges are checked here, per sequence)
+template <bool MODES>
+__device__ __forceinline__ void sample_step_body(
+    const float* __restrict__ logits, long ldl, int V, int eos_id, const SampParams sp, const SampState ss,
+    int32_t* __restrict__ state, int32_t* __restrict__ out_tokens, int max_out,
     int32_t* __restrict__ sampled, const int32_t* __restrict__ forced, const float* __restrict__ speech_emb, int E,
     float* __restrict__ next_x, long ldx, float* __restrict__ logp_out) {
     __shared__ float shf[SAMP_WAVES];
@@ -112,11 +129,18 @@ __global__ __launch_bounds__(SAMP_THREADS) void sample_step_kernel(
     const int nb = gridDim.x;                          // state is field-major: state[field * B + b]
     int32_t* st = state + b;
 #define ST(f) st[(f) * nb]
-    const int pos = ST(0), step = ST(1), n_out = ST(2), finished = ST(3), min_len = ST(4), max_len = ST(5), seq = ST(6);
-    if (finished) return;                              // uniform per block
+    const int pos = ss.pos, step = ss.step, n_out = ss.n_out, min_len = ss.min_len, max_len = ss.max_len, seq = ss.seq;
+    if (ss.finished) return;                           // uniform per block
+    const int mode = MODES ? sp.mode : SAMP_RAS, top_k = sp.top_k, win_size = sp.win_size;
+    const float top_p = sp.top_p, tau_r = sp.tau_r;
+    const unsigned long long seed = sp.seed;
+    if (MODES && ((unsigned)mode > 2u || top_k < 1 || top_k > SAMP_MAXK || (unsigned)win_size > 64u)) {
+        if (tid == 0) { ST(7) = SAMP_ERR_PARAMS; ST(3) = 1; }     // a bad column ends its own sequence, nothing is drawn
+        return;
+    }
     const float* lg = logits + (long)b * ldl;
     // the repetition window (common.py:113: the last win_size accepted tokens), one token per lane, requested with the logits
-    const int wn = min(win_size, n_out);
+    const int wn = mode == SAMP_RAS ? min(win_size, n_out) : 0;
     int hist = -1;
     if (lane < wn) hist = out_tokens[(long)b * max_out + n_out - wn + lane];
 
@@ -161,108 +185,118 @@ __global__ __launch_bounds__(SAMP_THREADS) void sample_step_kernel(
             p_lds[tid + i * SAMP_THREADS] = x[i];
         }
 
-    // nucleus candidates = prefix of the stable descending sort (value desc, index asc), found by RANK COUNTING
-    // rather than by repeated arg-max rounds: (1) the maximum of every group of 8 lanes (104 elements); (2) one wave counts,
-    // for each of the 64 group maxima, how many of the others precede it in the sort order - the one with rank top_k-1 is a
-    // threshold T with at least top_k elements >= T, so every global top_k element is >= T; (3) all elements >= T are pushed
-    // to a small LDS list; (4) each list entry's rank inside the list is its position in the sorted prefix; (5) the fp32
-    // running sum walks that prefix in the reference's order (common.py:124-131).  Ranks are unique because indices are.
-    auto precedes = [](float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); };
-    {
-        ArgMax a{-2.f, 0x7fffffff};
+    // (random-only columns skip the ranking work altogether: no group maxima, no list, no prefix walk)
+    float cp = 0.f;
+    int ci = 0, nc = 0;
+    if (mode != SAMP_RANDOM) {
+        // nucleus candidates = prefix of the stable descending sort (value desc, index asc), found by RANK COUNTING
+        // rather than by repeated arg-max rounds: (1) the maximum of every group of 8 lanes (104 elements); (2) one wave counts,
+        // for each of the 64 group maxima, how many of the others precede it in the sort order - the one with rank top_k-1 is a
+        // threshold T with at least top_k elements >= T, so every global top_k element is >= T; (3) all elements >= T are pushed
+        // to a small LDS list; (4) each list entry's rank inside the list is its position in the sorted prefix; (5) the fp32
+        // running sum walks that prefix in the reference's order (common.py:124-131).  Ranks are unique because indices are.
+        auto precedes = [](float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); };
+        {
+            ArgMax a{-2.f, 0x7fffffff};
 #pragma unroll
-        for (int i = 0; i < SAMP_MAXV; ++i) a = better(a, ArgMax{x[i], tid + i * SAMP_THREADS});
-        a = dpp_better<0xB1>(a);                       // lanes xor 1, xor 2, then the other quad of the 8
-        a = dpp_better<0x4E>(a);
-        a = dpp_better<0x141>(a);
-        if ((lane & 7) == 0) { gmax_p[tid >> 3] = a.v; gmax_i[tid >> 3] = a.i; }
-    }
-    if (tid == 0) sh_cnt = 0;
-    __syncthreads();
-    if (wave == 0) {
-        const float mv = gmax_p[lane];
-        const int mi = gmax_i[lane];
-        int rk = 0;
-#pragma unroll
-        for (int j = 0; j < SAMP_GROUPS; j += 4) {     // 16-byte broadcast reads
-            const float4 pv = *reinterpret_cast<const float4*>(gmax_p + j);
-            const int4 iv = *reinterpret_cast<const int4*>(gmax_i + j);
-            rk += (precedes(pv.x, iv.x, mv, mi) ? 1 : 0) + (precedes(pv.y, iv.y, mv, mi) ? 1 : 0) +
-                  (precedes(pv.z, iv.z, mv, mi) ? 1 : 0) + (precedes(pv.w, iv.w, mv, mi) ? 1 : 0);
+            for (int i = 0; i < SAMP_MAXV; ++i) a = better(a, ArgMax{x[i], tid + i * SAMP_THREADS});
+            a = dpp_better<0xB1>(a);                       // lanes xor 1, xor 2, then the other quad of the 8
+            a = dpp_better<0x4E>(a);
+            a = dpp_better<0x141>(a);
+            if ((lane & 7) == 0) { gmax_p[tid >> 3] = a.v; gmax_i[tid >> 3] = a.i; }
         }
-        if (rk == min(top_k, SAMP_GROUPS) - 1) { sh_thr_v = mv; sh_thr_i = mi; }
-    }
-    __syncthreads();
-    {
-        const ArgMax thr{sh_thr_v, sh_thr_i};
+        if (tid == 0) sh_cnt = 0;
+        __syncthreads();
+        if (wave == 0) {
+            const float mv = gmax_p[lane];
+            const int mi = gmax_i[lane];
+            int rk = 0;
 #pragma unroll
-        for (int i = 0; i < SAMP_MAXV; ++i) {
-            const ArgMax e{x[i], tid + i * SAMP_THREADS};
-            // e >= thr in the sort order  <=>  !(thr strictly precedes e)
-            const bool take = e.i < V && !precedes(thr.v, thr.i, e.v, e.i);
-            // one LDS atomic per wave and round instead of one per taker (the list's order is irrelevant: ranks are
-            // recomputed from (value, index) below)
-            const unsigned long long tm = __ballot(take);
-            if (tm) {
-                const int leader = __ffsll((long long)tm) - 1;
-                int base = 0;
-                if (lane == leader) base = atomicAdd(&sh_cnt, __popcll(tm));
-                base = __shfl(base, leader, 64);
-                if (take) {
-                    const int slot = base + __popcll(tm & ((1ull << lane) - 1ull));
-                    if (slot < SAMP_LIST) { list_p[slot] = e.v; list_i[slot] = e.i; }
+            for (int j = 0; j < SAMP_GROUPS; j += 4) {     // 16-byte broadcast reads
+                const float4 pv = *reinterpret_cast<const float4*>(gmax_p + j);
+                const int4 iv = *reinterpret_cast<const int4*>(gmax_i + j);
+                rk += (precedes(pv.x, iv.x, mv, mi) ? 1 : 0) + (precedes(pv.y, iv.y, mv, mi) ? 1 : 0) +
+                      (precedes(pv.z, iv.z, mv, mi) ? 1 : 0) + (precedes(pv.w, iv.w, mv, mi) ? 1 : 0);
+            }
+            if (rk == min(top_k, SAMP_GROUPS) - 1) { sh_thr_v = mv; sh_thr_i = mi; }
+        }
+        __syncthreads();
+        {
+            const ArgMax thr{sh_thr_v, sh_thr_i};
+#pragma unroll
+            for (int i = 0; i < SAMP_MAXV; ++i) {
+                const ArgMax e{x[i], tid + i * SAMP_THREADS};
+                // e >= thr in the sort order  <=>  !(thr strictly precedes e)
+                const bool take = e.i < V && !precedes(thr.v, thr.i, e.v, e.i);
+                // one LDS atomic per wave and round instead of one per taker (the list's order is irrelevant: ranks are
+                // recomputed from (value, index) below)
+                const unsigned long long tm = __ballot(take);
+                if (tm) {
+                    const int leader = __ffsll((long long)tm) - 1;
+                    int base = 0;
+                    if (lane == leader) base = atomicAdd(&sh_cnt, __popcll(tm));
+                    base = __shfl(base, leader, 64);
+                    if (take) {
+                        const int slot = base + __popcll(tm & ((1ull << lane) - 1ull));
+                        if (slot < SAMP_LIST) { list_p[slot] = e.v; list_i[slot] = e.i; }
+                    }
                 }
             }
         }
-    }
-    __syncthreads();
-    const int cnt = min(sh_cnt, SAMP_LIST);
-    // rank of list entry `id` inside the list: 8 lanes share the comparisons of one entry (64 entries per round)
-    for (int id0 = 0; id0 < cnt; id0 += SAMP_THREADS / 8) {
-        const int id = id0 + (tid >> 3), part = tid & 7;
-        const bool live = id < cnt;
-        const float mv = live ? list_p[id] : 0.f;
-        const int mi = live ? list_i[id] : 0;
-        int rk = 0;
-        for (int j = part; j < cnt; j += 8) rk += precedes(list_p[j], list_i[j], mv, mi) ? 1 : 0;
-        rk += __builtin_amdgcn_update_dpp(0, rk, 0xB1, 0xf, 0xf, false);
-        rk += __builtin_amdgcn_update_dpp(0, rk, 0x4E, 0xf, 0xf, false);
-        rk += __builtin_amdgcn_update_dpp(0, rk, 0x141, 0xf, 0xf, false);
-        if (live && part == 0 && rk < SAMP_MAXK) { cand_p[rk] = mv; cand_i[rk] = mi; }
-    }
-    __syncthreads();
-    // every wave walks the sorted prefix on its own (no barrier, no broadcast): lane i holds candidate i, the fp32 running sum
-    // adds them in the reference's order (common.py:127)
-    const int lim = min(min(top_k, SAMP_MAXK), cnt);
-    const float cp = lane < lim ? cand_p[lane] : 0.f;
-    const int ci = lane < lim ? cand_i[lane] : 0;
-    int nc = 0;
-    {
-        float cum = 0.f;
+        __syncthreads();
+        const int cnt = min(sh_cnt, SAMP_LIST);
+        // rank of list entry `id` inside the list: 8 lanes share the comparisons of one entry (64 entries per round)
+        for (int id0 = 0; id0 < cnt; id0 += SAMP_THREADS / 8) {
+            const int id = id0 + (tid >> 3), part = tid & 7;
+            const bool live = id < cnt;
+            const float mv = live ? list_p[id] : 0.f;
+            const int mi = live ? list_i[id] : 0;
+            int rk = 0;
+            for (int j = part; j < cnt; j += 8) rk += precedes(list_p[j], list_i[j], mv, mi) ? 1 : 0;
+            rk += __builtin_amdgcn_update_dpp(0, rk, 0xB1, 0xf, 0xf, false);
+            rk += __builtin_amdgcn_update_dpp(0, rk, 0x4E, 0xf, 0xf, false);
+            rk += __builtin_amdgcn_update_dpp(0, rk, 0x141, 0xf, 0xf, false);
+            if (live && part == 0 && rk < SAMP_MAXK) { cand_p[rk] = mv; cand_i[rk] = mi; }
+        }
+        __syncthreads();
+        // every wave walks the sorted prefix on its own (no barrier, no broadcast): lane i holds candidate i, the fp32 running sum
+        // adds them in the reference's order (common.py:127)
+        const int lim = min(min(top_k, SAMP_MAXK), cnt);
+        cp = lane < lim ? cand_p[lane] : 0.f;
+        ci = lane < lim ? cand_i[lane] : 0;
+        {
+            float cum = 0.f;
 #pragma unroll 1
-        while (cum < top_p && nc < lim) {
-            cum += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cp), nc));
-            nc++;
+            while (cum < top_p && nc < lim) {
+                cum += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cp), nc));
+                nc++;
+            }
         }
     }
 
     const bool ignore_eos = step < min_len;
     int top = 0;
     for (int trial = 0;; ++trial) {
-        // nucleus draw: argmax_i cand_p[i] / e_i, reduced inside every wave (the same values in each: no barrier)
-        ArgMax a{-1.f, 0x7fffffff};
-        if (lane < nc) a = ArgMax{cp / exp_noise(seed, seq, step, trial, 0, lane), lane};
+        bool full = mode == SAMP_RANDOM;                // common.py:137-139 alone
+        if (mode != SAMP_RANDOM) {
+            // nucleus draw: argmax_i cand_p[i] / e_i, reduced inside every wave (the same values in each: no barrier)
+            ArgMax a{-1.f, 0x7fffffff};
+            if (lane < nc) a = ArgMax{cp / exp_noise(seed, seq, step, trial, 0, lane), lane};
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            ArgMax y;
-            y.v = __shfl_xor(a.v, o, 64);
-            y.i = __shfl_xor(a.i, o, 64);
-            a = better(a, y);
+            for (int o = 32; o > 0; o >>= 1) {
+                ArgMax y;
+                y.v = __shfl_xor(a.v, o, 64);
+                y.i = __shfl_xor(a.i, o, 64);
+                a = better(a, y);
+            }
+            top = __builtin_amdgcn_readlane(ci, a.i);
+            // repetition-aware fallback (common.py:113-115); nucleus-only columns have no window
+            if (mode == SAMP_RAS) {
+                const int rep = __popcll(__ballot(hist == top));
+                full = (float)rep >= (float)win_size * tau_r;
+            }
         }
-        top = __builtin_amdgcn_readlane(ci, a.i);
-        // repetition-aware fallback (common.py:113-115)
-        const int rep = __popcll(__ballot(hist == top));
-        if ((float)rep >= (float)win_size * tau_r) {
+        if (full) {
             ArgMax r{-1.f, 0x7fffffff};
 #pragma unroll 1
             for (int idx = tid; idx < V; idx += SAMP_THREADS)      // rolled: p from LDS keeps this rare path compact
@@ -271,7 +305,7 @@ __global__ __launch_bounds__(SAMP_THREADS) void sample_step_kernel(
             top = r.i;
         }
         if (!ignore_eos || top != eos_id) break;
-        if (trial >= 100) { if (tid == 0) ST(7) = 1; break; }    // llm.py:271-273 raises here; flag + accept
+        if (trial >= 100) { if (tid == 0) ST(7) = SAMP_ERR_TRIALS; break; }    // llm.py:271-273 raises here; flag + accept
     }
     if (tid == 0 && sampled) sampled[(long)b * max_out + step] = top;
     if (forced) top = forced[(long)b * max_out + step];         // uniform: every thread reads the same word
@@ -291,6 +325,45 @@ __global__ __launch_bounds__(SAMP_THREADS) void sample_step_kernel(
 #undef ST
 }
 
+__global__ __launch_bounds__(SAMP_THREADS) void sample_step_kernel(
+    const float* __restrict__ logits, long ldl, int V, int eos_id, int top_k, float top_p, int win_size, float tau_r,
+    unsigned long long seed, int32_t* __restrict__ state, int32_t* __restrict__ out_tokens, int max_out,
+    int32_t* __restrict__ sampled, const int32_t* __restrict__ forced, const float* __restrict__ speech_emb, int E,
+    float* __restrict__ next_x, long ldx, float* __restrict__ logp_out) {
+    const int nb = gridDim.x;
+    const int32_t* st = state + blockIdx.x;
+    const SampState ss{st[0], st[nb], st[2 * nb], st[3 * nb], st[4 * nb], st[5 * nb], st[6 * nb]};
+    sample_step_body<false>(logits, ldl, V, eos_id, SampParams{SAMP_RAS, top_k, win_size, top_p, tau_r, seed}, ss, state, out_tokens,
+                            max_out, sampled, forced, speech_emb, E, next_x, ldx, logp_out);
+}
+
+// the table form: samp[field * B + b], fields {0 mode, 1 top_k, 2 win_size, 3 top_p bits, 4 tau_r bits, 5 seed lo, 6 seed hi}.
+// The 7 state words and the 7 table words of the sequence are fetched by ONE vector load (lanes 0..6 the state, 8..14 the table)
+// and handed out with v_readlane: one memory round trip before the `finished` test, as the scalar entry point has for its state
+// words alone.  (Written as two runs of scalar loads, the compiler sinks the table's below the `finished` branch: a second,
+// dependent round trip ahead of the logits.)
+__global__ __launch_bounds__(SAMP_THREADS) void sample_step_kernel_tab(
+    const float* __restrict__ logits, long ldl, int V, int eos_id, const int32_t* __restrict__ samp,
+    int32_t* __restrict__ state, int32_t* __restrict__ out_tokens, int max_out,
+    int32_t* __restrict__ sampled, const int32_t* __restrict__ forced, const float* __restrict__ speech_emb, int E,
+    float* __restrict__ next_x, long ldx, float* __restrict__ logp_out) {
+    const int nb = gridDim.x, lane = threadIdx.x & 63, f = lane & 7;
+    const int32_t* src = (lane & 8) ? samp : state;
+    int w = 0;
+    if (lane < 16 && f < 7) w = src[(long)f * nb + blockIdx.x];
+    auto word = [&](int l) { return __builtin_amdgcn_readlane(w, l); };
+    const SampState ss{word(0), word(1), word(2), word(3), word(4), word(5), word(6)};
+    SampParams sp;
+    sp.mode = word(8);
+    sp.top_k = word(9);
+    sp.win_size = word(10);
+    sp.top_p = __builtin_bit_cast(float, word(11));
+    sp.tau_r = __builtin_bit_cast(float, word(12));
+    sp.seed = (unsigned long long)(unsigned)word(13) | ((unsigned long long)(unsigned)word(14) << 32);
+    sample_step_body<true>(logits, ldl, V, eos_id, sp, ss, state, out_tokens, max_out, sampled, forced, speech_emb, E, next_x, ldx,
+                           logp_out);
+}
+
 extern "C" int mmx_sample_step(const float* logits, int64_t ldl, int V, int B, int eos_id, int top_k, float top_p,
                                int win_size, float tau_r, uint64_t seed, int32_t* state, int32_t* out_tokens, int max_out,
                                int32_t* sampled, const int32_t* forced, const float* speech_emb, int E, float* next_x,
@@ -299,6 +372,17 @@ extern "C" int mmx_sample_step(const float* logits, int64_t ldl, int V, int B, i
     MMX_CHECK_ARG(top_k > 0 && top_k <= SAMP_MAXK && top_k <= SAMP_GROUPS && win_size >= 0 && win_size <= 64 && max_out > 0 && E > 0 && eos_id < V);
     hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(SAMP_THREADS), 0, stream, logits, ldl, V, eos_id, top_k, top_p, win_size,
                        tau_r, (unsigned long long)seed, state, out_tokens, max_out, sampled, forced, speech_emb, E, next_x, ldx, logp_out);
+    MMX_LAUNCH_CHECK();
+    return MMX_OK;
+}
+
+extern "C" int mmx_sample_step_tab(const float* logits, int64_t ldl, int V, int B, int eos_id, const int32_t* samp, int32_t* state,
+                                   int32_t* out_tokens, int max_out, int32_t* sampled, const int32_t* forced,
+                                   const float* speech_emb, int E, float* next_x, int64_t ldx, float* logp_out, hipStream_t stream) {
+    MMX_CHECK_ARG(logits && samp && state && out_tokens && speech_emb && next_x && B > 0 && V > 0 && V <= SAMP_THREADS * SAMP_MAXV);
+    MMX_CHECK_ARG(max_out > 0 && E > 0 && eos_id < V);     // the column's own ranges are checked per sequence in the kernel
+    hipLaunchKernelGGL(sample_step_kernel_tab, dim3(B), dim3(SAMP_THREADS), 0, stream, logits, ldl, V, eos_id, samp, state, out_tokens,
+                       max_out, sampled, forced, speech_emb, E, next_x, ldx, logp_out);
     MMX_LAUNCH_CHECK();
     return MMX_OK;
 }

@@ -9,6 +9,8 @@ append, paged GQA attention, o_proj + residual, RMSNorm-folded gate/up + SwiGLU,
 device-resident sampler; it is recorded once into a hipGraph and replayed per token, with all loop state
 (positions, step counters, token history, next input embedding, finished flags) on the device — the host only
 polls `finished` every few steps (the reference syncs on .item() every token, llm.py:752).
+The sampler's parameters (mode, top_p, top_k, win_size, tau_r, seed) are device state too: one column per sequence of the
+table `samp` (include/mmx_hip.h, mmx_sample_step_tab), so every request has its own and the recorded step holds none of them.
 Attention is full causal over the KV cache (SURVEY.md §7 "version-drift trap").
 """
 import math
@@ -181,8 +183,12 @@ class LlmEngine:
         self.logits = torch.zeros(B, self.V, device=self.dev)
         self.logp = torch.zeros(B, self.V, device=self.dev)
         self.want_logp = False
+        # the engine's default sampler (config.yaml:46-50): what a sequence gets that is started without one of its own
         self.seed = 0
-        self.top_p, self.top_k, self.win_size, self.tau_r = 0.8, 25, 10, 0.1     # config.yaml:46-50
+        self.mode, self.top_p, self.top_k, self.win_size, self.tau_r = 0, 0.8, 25, 10, 0.1
+        # the sampler table the kernel reads (field-major, one column per slot) and its host mirror
+        self._samp_host = [self._sampler_fields(None, None) for _ in range(B)]
+        self.samp = torch.tensor([ops.sampler_column(**f) for f in self._samp_host], dtype=torch.int32).t().contiguous().to(self.dev)
         self._decode = None
         self.reserve_ahead = 1 << 30               # start(): rows reserved past the prompt (default: the whole max_len)
 
@@ -323,10 +329,44 @@ class LlmEngine:
         else:
             ops.skinny_gemm(self.h_act, self.wdec, B=B, K=self.H, N=self.V, dtype=self.dtype, bias=self.bdec, rs=True,
                             eps=self.eps, epi=0, out_f32=self.logits, x_packed=packed)
-        ops.sample_step(self.logits, self.state, self.out_tokens, self.speech_emb, self.x_in, V=self.V, B=B,
-                        eos_id=self.eos, seed=self.seed, top_k=self.top_k, top_p=self.top_p, win_size=self.win_size,
-                        tau_r=self.tau_r, sampled=self.sampled, forced=self.forced,
-                        logp_out=(self.logp if self.want_logp else None))
+        ops.sample_step_tab(self.logits, self.state, self.out_tokens, self.speech_emb, self.x_in, self.samp, V=self.V, B=B,
+                            eos_id=self.eos, sampled=self.sampled, forced=self.forced,
+                            logp_out=(self.logp if self.want_logp else None))
+
+    # ------------------------------------------------------------------ per-sequence samplers
+    SAMPLER_FIELDS = ("mode", "top_p", "top_k", "win_size", "tau_r", "seed")
+
+    def _sampler_fields(self, sampler, seed):
+        """The engine's default sampler overridden by `sampler` (a dict over SAMPLER_FIELDS, or None) and `seed` (or None)."""
+        f = {k: getattr(self, k) for k in self.SAMPLER_FIELDS}
+        if sampler:
+            unknown = set(sampler) - set(self.SAMPLER_FIELDS)
+            if unknown:
+                raise ValueError(f"unknown sampler fields {sorted(unknown)}")
+            f.update({k: v for k, v in sampler.items() if v is not None})
+        if seed is not None:
+            f["seed"] = int(seed)
+        f["mode"] = ops.SAMPLER_MODES.get(f["mode"], f["mode"])      # the mirror holds the mode as the table does: 0 / 1 / 2
+        return f
+
+    def _write_samplers(self, fields):
+        """fields: one dict per slot, len(fields) == B -> host mirror and device table, one copy."""
+        assert len(fields) == self.B
+        cols = [ops.sampler_column(**f) for f in fields]           # raises ValueError on a bad column: nothing written
+        self._samp_host = [dict(f) for f in fields]
+        self.samp.copy_(torch.tensor(cols, dtype=torch.int32).t().contiguous())
+
+    def set_sampler(self, slot: int, *, mode=None, top_p=None, top_k=None, win_size=None, tau_r=None, seed=None):
+        """Changes the sampler of one slot: the fields given (mode 0 / "ras", 1 / "nucleus", 2 / "random"; top_k 1..64; win_size
+        0..64), the others stay as the slot has them.  Takes effect at the slot's next sampling step, recorded decode graph included:
+        the kernel reads the column from device memory (csrc/sampler.hip)."""
+        f = dict(self._samp_host[slot])
+        f.update({k: v for k, v in dict(mode=mode, top_p=top_p, top_k=top_k, win_size=win_size, tau_r=tau_r, seed=seed).items()
+                  if v is not None})
+        f["mode"] = ops.SAMPLER_MODES.get(f["mode"], f["mode"])
+        col = ops.sampler_column(**f)
+        self._samp_host[slot] = f
+        self.samp[:, slot].copy_(torch.tensor(col, dtype=torch.int32))
 
     def _decode_step(self):
         B = self.B
@@ -394,14 +434,18 @@ class LlmEngine:
                 self._set_pages(s_, pos[s_] + 1 + ahead)
 
     @torch.no_grad()
-    def admit(self, slot: int, x: torch.Tensor, min_len: int, max_len: int, seq_id: int, ahead: Optional[int] = None):
+    def admit(self, slot: int, x: torch.Tensor, min_len: int, max_len: int, seq_id: int, ahead: Optional[int] = None,
+              sampler: Optional[dict] = None, seed: Optional[int] = None):
         """Continuous batching: puts a new request into an idle slot while the other slots keep decoding.  All prompt
         rows but the last are prefetched into freshly allocated pages; the last row becomes the slot's next input, so the
         next ordinary decode step of the batch computes its logits and draws its first token (same Philox key (seed,
         seq id, step 0) as a fixed-batch start) — no separate sampling pass, nothing of the other sequences is touched.
         ahead: cache rows reserved past the prompt.  None reserves the whole max_len (what start() does); a caller that
         passes less MUST call ensure_capacity() between decode steps (run_queue does) — rows past the reservation map to
-        the shared scratch page."""
+        the shared scratch page.
+        sampler / seed: the request's own (see start); None = the engine's attributes."""
+        fields = self._sampler_fields(sampler, seed)
+        ops.sampler_column(**fields)                      # a bad sampler is refused before the slot is touched
         L = x.shape[0]
         if L + max_len > self.max_pages * self.page:
             raise RuntimeError("sequence exceeds the KV cache")
@@ -413,15 +457,20 @@ class LlmEngine:
         self.x_in[slot].copy_(x[L - 1])
         st = torch.tensor([L - 1, 0, 0, 0, min_len, max_len, seq_id, 0], dtype=torch.int32)
         self.state[:, slot].copy_(st)
+        self.set_sampler(slot, **fields)
         self.sampled[slot].fill_(-1)
 
     def start(self, lm_inputs: List[torch.Tensor], min_lens: List[int], max_lens: List[int], seed=0, seq_ids=None,
-              forced: Optional[torch.Tensor] = None, want_logp=False):
+              forced: Optional[torch.Tensor] = None, want_logp=False, samplers: Optional[list] = None,
+              seeds: Optional[list] = None):
         """Prefills every sequence (prompt rows in chunks of <= 64 through the same kernels as decode) and samples
-        the first token of each.  After this, call step()/run()."""
+        the first token of each.  After this, call step()/run().
+        samplers: per sequence, a dict over (mode, top_p, top_k, win_size, tau_r, seed) or None; fields left out, and None, mean
+        the engine's attributes of those names.  seeds: per sequence, overrides the scalar `seed` (which becomes the engine's)."""
         B = self.B
-        assert len(lm_inputs) == B
+        assert len(lm_inputs) == B and (samplers is None or len(samplers) == B) and (seeds is None or len(seeds) == B)
         self.seed, self.want_logp = int(seed), want_logp
+        self._write_samplers([self._sampler_fields(samplers[b] if samplers else None, seeds[b] if seeds else None) for b in range(B)])
         if forced is not None:
             if self._forced_buf is None:
                 self._forced_buf = torch.zeros(B, self.max_out, dtype=torch.int32, device=self.dev)
@@ -454,10 +503,11 @@ class LlmEngine:
         self._tail(B)
         if self._decode is None:
             self._decode = Graphed(self._decode_step, self.use_graphs)
-        elif self._graph_key != (self.forced is None, want_logp, self.seed):
+        elif self._graph_key != (self.forced is None, want_logp):
             self._decode.release()
-            self._decode = Graphed(self._decode_step, self.use_graphs)      # baked arguments changed: re-record
-        self._graph_key = (self.forced is None, want_logp, self.seed)
+            self._decode = Graphed(self._decode_step, self.use_graphs)      # baked POINTERS changed: re-record
+        # (forced and logp_out are pointer arguments of the sampler launch; seeds and sampler parameters are device data)
+        self._graph_key = (self.forced is None, want_logp)
 
     def _prefill_batch(self, lm_inputs):
         """All prompts in one pass per layer: rows = B x Lmax (shorter prompts are zero padded; a padded row only adds
@@ -584,10 +634,11 @@ class LlmEngine:
         self.block_table.fill_(self.trash_page)           # idle slots append their (ignored) KV to the scratch page
         self.block_table[:n].copy_(big.block_table[ii])
         self.seed, self.want_logp = big.seed, False
-        self.top_p, self.top_k, self.win_size, self.tau_r = big.top_p, big.top_k, big.win_size, big.tau_r
+        self.mode, self.top_p, self.top_k, self.win_size, self.tau_r = big.mode, big.top_p, big.top_k, big.win_size, big.tau_r
+        self.samp[:, :n] = big.samp[:, ii]                # every survivor keeps its own sampler and seed
+        self._samp_host[:n] = [dict(big._samp_host[i]) for i in idx]
         self.forced = None
-        key = (True, False, self.seed)
-        self._fresh_decode_graph(key)
+        self._fresh_decode_graph((True, False))
 
     def _fresh_decode_graph(self, key):
         if self._decode is None or getattr(self, "_graph_key", None) != key:
@@ -612,12 +663,13 @@ class LlmEngine:
 
     @torch.no_grad()
     def run_queue(self, requests, seed=0, poll_every: int = 8, ahead: int = 32):
-        """Continuous batching over a queue of requests [(lm_input [L, H], min_len, max_len)]: up to B run at a time; when
-        a sequence finishes its pages go back to the allocator and the next queued request is admitted into its slot
+        """Continuous batching over a queue of requests [(lm_input [L, H], min_len, max_len[, sampler[, seed]])]: up to B run at a
+        time; when a sequence finishes its pages go back to the allocator and the next queued request is admitted into its slot
         between two decode steps.  Returns the accepted tokens per request (seq id = request index, so the result equals
-        running every request alone under the same seed)."""
+        running every request alone under the same seed and sampler).  A request's sampler (dict, see start) and seed are
+        optional; None / absent = the engine's sampler attributes and `seed`."""
         self.seed, self.want_logp, self.forced = int(seed), False, None
-        self._fresh_decode_graph((True, False, self.seed))
+        self._fresh_decode_graph((True, False))
         st = torch.zeros(8, self.B, dtype=torch.int32)
         st[ST_FIN] = 1
         self.state.copy_(st)
@@ -635,8 +687,9 @@ class LlmEngine:
                     owner[s_] = -1
                     self.release(s_)
                 if owner[s_] < 0 and nxt < len(requests):
-                    x, mn, mx = requests[nxt]
-                    self.admit(s_, x, mn, mx, seq_id=nxt, ahead=ahead + poll_every)
+                    x, mn, mx, *own = requests[nxt]
+                    self.admit(s_, x, mn, mx, seq_id=nxt, ahead=ahead + poll_every, sampler=(own[0] if own else None),
+                               seed=(own[1] if len(own) > 1 else None))
                     owner[s_] = nxt
                     nxt += 1
             active = [s_ for s_ in range(self.B) if owner[s_] >= 0]
@@ -647,7 +700,7 @@ class LlmEngine:
                 self._decode()
 
     # ------------------------------------------------------------------ host-driven stream (bistream decode, llm.py:762-870)
-    def open_stream(self, seed=0, seq_id=0, want_logp=False):
+    def open_stream(self, seed=0, seq_id=0, want_logp=False, sampler: Optional[dict] = None):
         """One sequence (slot 0) whose LM passes are issued one at a time by the host: text rows and speech-token rows
         arrive interleaved, so the loop of llm.py:786-870 stays on the host; every pass still runs on the HIP kernels and
         the sampler stays on the device.  The loop state (fields of include/mmx_hip.h) is mirrored on the host and
@@ -656,9 +709,10 @@ class LlmEngine:
         self.release(0)
         self._set_pages(0, self.max_pages * self.page)        # the text arrives incrementally: reserve the whole context
         self.seed, self.want_logp, self.forced = int(seed), bool(want_logp), None
+        self._write_samplers([self._sampler_fields(sampler, None)])
         self._st = dict(rows=0, calls=0, hist=0, seq=int(seq_id), last=None)
         self.sampled.fill_(-1)
-        self._fresh_decode_graph((True, self.want_logp, self.seed))
+        self._fresh_decode_graph((True, self.want_logp))
 
     def embed_text(self, tok: torch.Tensor) -> torch.Tensor:
         """llm.model.model.embed_tokens rows, fp32 [n, H]."""
@@ -702,7 +756,10 @@ class LlmEngine:
             self._upload_state(s["rows"] + n - 1, ignore_eos)
             self._tail(1)
         tok = int(self.sampled[0, s["calls"]].item())
-        if int(self.state[7, 0].item()):
+        err = int(self.state[ST_ERR, 0].item())
+        if err == 2:
+            raise RuntimeError("the sampler table's column is out of range (include/mmx_hip.h, mmx_sample_step_tab)")
+        if err:
             raise RuntimeError("sampling reaches max_trials 100 and still get eos when ignore_eos is True, check your input!")
         s["rows"] += n
         s["calls"] += 1

@@ -501,3 +501,28 @@ def sample_step(logits, state, out_tokens, speech_emb, next_x, *, V, B, eos_id, 
                                  C.c_float(tau_r), C.c_uint64(seed), _p(state), _p(out_tokens), out_tokens.shape[1],
                                  _p(sampled), _p(forced), _p(speech_emb), speech_emb.shape[1], _p(next_x),
                                  i64(next_x.shape[-1]), _p(logp_out), stream()), "mmx_sample_step")
+
+
+SAMP_MODE, SAMP_TOP_K, SAMP_WIN, SAMP_TOP_P, SAMP_TAU_R, SAMP_SEED_LO, SAMP_SEED_HI = range(7)   # fields of the sampler table
+SAMPLER_MODES = {"ras": 0, "nucleus": 1, "random": 2}
+
+
+def sampler_column(mode=0, top_p=0.8, top_k=25, win_size=10, tau_r=0.1, seed=0):
+    """One column of the sampler table of mmx_sample_step_tab (include/mmx_hip.h) as 8 int32 words; range-checked like the kernel
+    checks it."""
+    import struct
+    mode = SAMPLER_MODES.get(mode, mode)
+    if mode not in (0, 1, 2) or not 1 <= int(top_k) <= 64 or not 0 <= int(win_size) <= 64:
+        raise ValueError(f"sampler out of range: mode {mode!r} (0..2), top_k {top_k} (1..64), win_size {win_size} (0..64)")
+    bits = lambda v: struct.unpack("<i", struct.pack("<f", float(v)))[0]
+    i32 = lambda u: u - (1 << 32) if u >= (1 << 31) else u
+    seed = int(seed) & ((1 << 64) - 1)
+    return [int(mode), int(top_k), int(win_size), bits(top_p), bits(tau_r), i32(seed & 0xffffffff), i32(seed >> 32), 0]
+
+
+def sample_step_tab(logits, state, out_tokens, speech_emb, next_x, samp, *, V, B, eos_id, sampled=None, forced=None, logp_out=None):
+    """mmx_sample_step with every sequence's sampler in the device table samp int32 [8, B] (sampler_column per column)."""
+    assert samp.dtype == torch.int32 and samp.is_contiguous() and samp.shape == (8, B)
+    check(load().mmx_sample_step_tab(_p(logits), i64(logits.shape[-1]), V, B, eos_id, _p(samp), _p(state), _p(out_tokens),
+                                     out_tokens.shape[1], _p(sampled), _p(forced), _p(speech_emb), speech_emb.shape[1],
+                                     _p(next_x), i64(next_x.shape[-1]), _p(logp_out), stream()), "mmx_sample_step_tab")

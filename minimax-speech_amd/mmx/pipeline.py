@@ -106,9 +106,10 @@ class TtsEngine:
 
     @torch.no_grad()
     def generate_tokens(self, texts: List[torch.Tensor], prompt_texts=None, prompt_speech=None, seed=0,
-                        min_ratio=2, max_ratio=20, exact_steps=None) -> List[torch.Tensor]:
+                        min_ratio=2, max_ratio=20, exact_steps=None, samplers=None, seeds=None) -> List[torch.Tensor]:
         """Batched AR decode (Qwen2LM.inference semantics per sequence). exact_steps (int or list) forces exactly
-        that many sampling steps with EOS ignored (BASELINE config 3: 250 steps for a 10 s utterance)."""
+        that many sampling steps with EOS ignored (BASELINE config 3: 250 steps for a 10 s utterance).
+        samplers / seeds: per utterance (LlmEngine.start); None = the LM engine's sampler attributes and the scalar `seed`."""
         B = len(texts)
         assert B == self.llm.B
         if exact_steps is not None and not isinstance(exact_steps, (list, tuple)):
@@ -122,7 +123,7 @@ class TtsEngine:
             n = texts[b].numel()
             mins.append(exact_steps[b] if exact_steps is not None else int(n * min_ratio))
             maxs.append(exact_steps[b] if exact_steps is not None else int(n * max_ratio))
-        self.llm.start(xs, mins, maxs, seed=seed)
+        self.llm.start(xs, mins, maxs, seed=seed, samplers=samplers, seeds=seeds)
         self.llm.run(max(maxs))
         n = self.llm.state[2].tolist()
         return [self.llm.out_tokens[b, :n[b]].to(torch.int64) for b in range(B)]
@@ -401,7 +402,7 @@ class TtsEngine:
     def tts_batch(self, texts, flow_embeddings, seed=0, exact_steps=None, group_size=8, max_pad_ratio=2.0,
                   frame_quantum=32, overlap=True, poll_every=8, flow_workers=2, hold_steps=60, tail_active=0, polite=True,
                   prompt_texts=None, llm_prompt_speech_tokens=None, flow_prompt_speech_tokens=None,
-                  prompt_speech_feats=None) -> List[torch.Tensor]:
+                  prompt_speech_feats=None, samplers=None, seeds=None) -> List[torch.Tensor]:
         """Throughput path for a batch of independent utterances (BASELINE config 4, one rank's share): one batched
         AR decode for all of them; as sequences finish (shortest first) their flow + DAC work — per-utterance
         conformer encoder, ODE solves batched over groups of similar length (zero padded + masked), DAC decode — is
@@ -411,6 +412,8 @@ class TtsEngine:
         Zero-shot prompts (cli/cosyvoice.py:92-104 -> cli/model.py:321-326), each a per-utterance list or None: prompt_texts
         and llm_prompt_speech_tokens condition the LM (llm.py:691-703), flow_prompt_speech_tokens / prompt_speech_feats the
         flow (flow.py:472-498).
+        samplers / seeds: per utterance, the LM sampler (dict over mode / top_p / top_k / win_size / tau_r / seed, LlmEngine.start)
+        and seed of its own; None (the list or an entry) = the LM engine's sampler attributes and the scalar `seed`.
         group_size / hold_steps: a finished utterance waits at most hold_steps decode steps for up to group_size companions
         of similar length.  Large groups pay twice: a launch of the fused flow kernels costs about the same from 500 to
         8 000 rows (it is bound by every workgroup streaming the block's weights), so fewer, fuller groups are less GPU
@@ -430,6 +433,8 @@ class TtsEngine:
         B = len(texts)
         NS = self.llm.B                                   # decode slots; more utterances than slots queue up and are admitted
         assert B >= NS and (overlap or B == NS)           # into slots as they free (continuous batching, LlmEngine.admit)
+        assert (samplers is None or len(samplers) == B) and (seeds is None or len(seeds) == B)
+        own = lambda lst, b: None if lst is None else lst[b]
         if exact_steps is not None and not isinstance(exact_steps, (list, tuple)):
             exact_steps = [exact_steps] * B
         z = torch.zeros(1, 0, dtype=torch.long, device=self.dev)
@@ -447,7 +452,7 @@ class TtsEngine:
         wavs: List[Optional[torch.Tensor]] = [None] * B
         toks: List[Optional[torch.Tensor]] = [None] * B
         if not overlap:
-            self.llm.start(xs, mins, maxs, seed=seed)
+            self.llm.start(xs, mins, maxs, seed=seed, samplers=samplers, seeds=seeds)
             self.llm.run(max(maxs), poll_every)
             n = self.llm.state[ST_NOUT].tolist()
             for b in range(B):
@@ -535,7 +540,7 @@ class TtsEngine:
                 if not free:
                     break
                 s_, b = free[0], waiting.pop(0)
-                eng.admit(s_, xs[b], mins[b], maxs[b], seq_id=b)    # reserves KV pages for the whole max_len
+                eng.admit(s_, xs[b], mins[b], maxs[b], seq_id=b, sampler=own(samplers, b), seed=own(seeds, b))   # reserves KV pages for the whole max_len
                 slots[s_] = b
                 fin[s_] = 0
             if not final and eng is self.llm:
@@ -587,7 +592,8 @@ class TtsEngine:
                     pending.remove(b)
 
         with torch.cuda.stream(main):
-            self.llm.start(xs[:NS], mins[:NS], maxs[:NS], seed=seed)   # (captures serialise themselves: mmx/flow.py, Graphed)
+            self.llm.start(xs[:NS], mins[:NS], maxs[:NS], seed=seed, samplers=samplers and samplers[:NS],
+                           seeds=seeds and seeds[:NS])              # (captures serialise themselves: mmx/flow.py, Graphed)
             # without a queue max(maxs) steps end every sequence; with one, admissions happen only at polls, so the loop
             # runs until every utterance has been seen (the bound only stops a runaway: each admitted utterance can wait
             # up to poll_every steps for its slot on top of its own max_len)

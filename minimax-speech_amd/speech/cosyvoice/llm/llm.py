@@ -150,6 +150,21 @@ class Qwen2LM(EngineHost):
         kw.update(getattr(self.sampling, "keywords", None) or {})
         return kw
 
+    def _sampler_spec(self):
+        """`self.sampling` as a device sampler (the dict LlmEngine.start takes), or None for a callable the device does not
+        know, which then runs on the host at every step (_decode_loop_host).  The three samplers of utils/common.py:111-139 map to
+        the sampler kernel's modes; keywords bound with functools.partial are read, the others are the functions' defaults."""
+        from cosyvoice.utils import common
+        fn = getattr(self.sampling, "func", self.sampling)
+        kw = self._sampling_kwargs()
+        if fn is common.ras_sampling:
+            return dict(mode=0, top_p=kw["top_p"], top_k=kw["top_k"], win_size=kw["win_size"], tau_r=kw["tau_r"])
+        if fn is common.nucleus_sampling:
+            return dict(mode=1, top_p=kw["top_p"], top_k=kw["top_k"])
+        if fn is common.random_sampling:
+            return dict(mode=2)
+        return None
+
     def engine(self, max_batch=1):
         from mmx.llm import LlmEngine
         dev = self._device()
@@ -159,9 +174,8 @@ class Qwen2LM(EngineHost):
                                      max_ctx=self.max_ctx, heads=c["num_attention_heads"], kv_heads=c["num_key_value_heads"],
                                      head_dim=c["hidden_size"] // c["num_attention_heads"], rope_theta=c["rope_theta"],
                                      eps=c["rms_norm_eps"], speech_token_size=self.speech_token_size)
-            kw = self._sampling_kwargs()
-            self._engine.top_p, self._engine.top_k = kw["top_p"], kw["top_k"]
-            self._engine.win_size, self._engine.tau_r = kw["win_size"], kw["tau_r"]
+            for k, v in (self._sampler_spec() or {}).items():     # the engine's default sampler = the configured one
+                setattr(self._engine, k, v)                          # (a host callable leaves the engine's own defaults)
         return self._engine
 
     @torch.inference_mode()
@@ -190,7 +204,7 @@ class Qwen2LM(EngineHost):
         else:
             spk = torch.zeros(1, self.llm_input_size, device=eng.dev)
         x = eng.build_lm_input(text, prompt_text, prompt_speech_token, speaker_embed=spk)
-        yield from self._decode_loop(eng, x, int(tl * min_token_text_ratio), int(tl * max_token_text_ratio))
+        yield from self._decode_loop(eng, x, int(tl * min_token_text_ratio), int(tl * max_token_text_ratio), sampling)
 
     @torch.inference_mode()
     def inference(self, text: torch.Tensor, text_len: torch.Tensor, prompt_text: torch.Tensor,
@@ -203,20 +217,21 @@ class Qwen2LM(EngineHost):
         tl = int(text.shape[1])
         text_len += prompt_text_len                      # the reference mutates text_len in place (llm.py:693)
         x = eng.build_lm_input(text, prompt_text, prompt_speech_token)
-        yield from self._decode_loop(eng, x, int(tl * min_token_text_ratio), int(tl * max_token_text_ratio))
+        yield from self._decode_loop(eng, x, int(tl * min_token_text_ratio), int(tl * max_token_text_ratio), sampling)
 
     @torch.inference_mode()
     def inference_wrapper(self, lm_input, sampling, min_len, max_len, uuid):
         """llm.py:713-760, non-vLLM branch: the AR loop over a prepared lm_input [1, L, H] — batched prompt pass, captured
-        decode step, log-softmax + RAS + stop / skip rules on the device (mmx/llm.py, csrc/sampler.hip)."""
-        yield from self._decode_loop(self.engine(1), lm_input[0], int(min_len), int(max_len))
+        decode step, log-softmax + the configured sampler + stop / skip rules on the device (mmx/llm.py, csrc/sampler.hip); a
+        `self.sampling` the device does not know is called on the host at every step."""
+        yield from self._decode_loop(self.engine(1), lm_input[0], int(min_len), int(max_len), sampling)
 
     def _is_device_sampler(self):
-        from cosyvoice.utils.common import ras_sampling
-        return getattr(self.sampling, "func", self.sampling) is ras_sampling
+        return self._sampler_spec() is not None
 
     def sampling_ids(self, weighted_scores: torch.Tensor, decoded_tokens: List, sampling: int, ignore_eos: bool = True):
-        """llm.py:259-274 around a host `sampling` callable (used by inference_bistream when `sampling` is not RAS)."""
+        """llm.py:259-274 around a host `sampling` callable (used by every inference path when `sampling` is none of the three
+        samplers the device runs, _sampler_spec)."""
         num_trials, max_trials = 0, 100
         while True:
             top_ids = self.sampling(weighted_scores, decoded_tokens, sampling)
@@ -240,12 +255,12 @@ class Qwen2LM(EngineHost):
         device log-probs, as the reference would call it."""
         eng = self.engine(1)
         dev_sampler = self._is_device_sampler()
-        eng.open_stream(seed=self.seed, want_logp=not dev_sampler)
+        eng.open_stream(seed=self.seed, want_logp=not dev_sampler, sampler=self._sampler_spec())
         fill, n_speech = self.speech_token_size + 2, self.speech_token_size
         mix = self.mix_ratio
 
         def step(x, ignore_eos, out_tokens, forced=None):
-            tok = eng.feed(x, ignore_eos)
+            tok = eng.feed(x, ignore_eos and dev_sampler)      # (a host sampler does its own re-draws: the device's draw is unused)
             if forced is not None:                        # llm.py:824-826: the pass runs, its draw is not used
                 return forced
             if not dev_sampler:
@@ -310,8 +325,35 @@ class Qwen2LM(EngineHost):
             yield top_ids
             lm_input, pending = eng.x_in[0:1], True
 
-    def _decode_loop(self, eng, x, min_len, max_len):
-        eng.start([x], [min_len], [max_len], seed=self.seed)
+    def _decode_loop_host(self, eng, x, min_len, max_len, sampling=25):
+        """llm.py:745-760 around a `self.sampling` the device does not know: every LM pass and the log-softmax run on the
+        device, the callable is called from the pass's log-probs through sampling_ids (llm.py:259-274) exactly as the reference
+        calls it, once per step (more under ignore_eos when it returns EOS)."""
+        if x.shape[0] + max_len > eng.max_pages * eng.page:
+            raise RuntimeError("sequence exceeds the KV cache")
+        eng.open_stream(seed=self.seed, want_logp=True)
+        eos, out_tokens = self.speech_token_size, []
+        lm_input = x                                      # None: the embedding of the last accepted token (eng.x_in)
+        for i in range(max_len):
+            eng.feed(lm_input, False)                     # (the device's own draw is not used)
+            top_ids = int(self.sampling_ids(eng.logp[0], out_tokens, sampling, ignore_eos=i < min_len))
+            if top_ids == eos:
+                break
+            if top_ids > eos:                             # llm.py:755-756: no yield, lm_input is NOT updated (it is fed again)
+                if lm_input is None:
+                    eng.x_in[0].copy_(eng.speech_emb[out_tokens[-1]])      # the device's unused draw may have moved x_in
+                continue
+            eng.commit(top_ids)
+            yield top_ids
+            out_tokens.append(top_ids)
+            lm_input = None
+
+    def _decode_loop(self, eng, x, min_len, max_len, sampling=25):
+        spec = self._sampler_spec()
+        if spec is None:
+            yield from self._decode_loop_host(eng, x, min_len, max_len, sampling)
+            return
+        eng.start([x], [min_len], [max_len], seed=self.seed, samplers=[spec])
         sent = 0
         done = 1
         while True:
