@@ -12,6 +12,9 @@ polls `finished` every few steps (the reference syncs on .item() every token, ll
 The sampler's parameters (mode, top_p, top_k, win_size, tau_r, seed) are device state too: one column per sequence of the
 table `samp` (include/mmx_hip.h, mmx_sample_step_tab), so every request has its own and the recorded step holds none of them.
 Attention is full causal over the KV cache (SURVEY.md §7 "version-drift trap").
+LmModel holds what engines of different batch sizes share (packed weights, RoPE tables, paged KV cache, page allocator);
+an LlmEngine is one batch size over it and decides at construction which kernel family runs its decode step and its prompt
+rows (decode_on / prompt_on, LlmEngine._dispatch), refusing the combinations no kernel serves.
 """
 import math
 from typing import Dict, List, Optional
@@ -49,6 +52,78 @@ class PageAllocator:
         self.free_pages.extend(reversed(pages))
 
 
+class LmModel:
+    """What every engine over one checkpoint shares, built once from the state dict: shapes and flags, the packed weights, the
+    RoPE tables, the paged KV cache and its page allocator.  An LlmEngine adds what belongs to one batch size."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], dtype, device, max_batch, max_ctx, page, heads, kv_heads, head_dim, rope_theta,
+                 eps, speech_token_size, prefix, kv_pages, wplanes, h2, gemm_packs):
+        """wplanes / h2: the decode packs are weight planes / fp16 (w * 2^8); gemm_packs: row-major copies for the windowed GEMM
+        are packed too.  max_batch sizes the KV cache when kv_pages is None."""
+        self.dtype, self.tdt, self.dev = dtype, TORCH_DT[dtype], torch.device(device)
+        self.wplanes, self.h2 = wplanes, h2
+        self.ddt = H2 if h2 else dtype                    # dtype code of the decode-step kernels (csrc/decode.hip)
+        self.split = is_split(dtype)                      # bf16 weights, fp32 activations split inside the MFMA products
+        self.Hq, self.Hkv, self.D, self.eps, self.page = heads, kv_heads, head_dim, eps, page
+        self.eos, self.V = speech_token_size, speech_token_size + 3
+        f = lambda k: sd[k].detach().to(self.dev, torch.float32).contiguous()
+        c = (lambda t: t.float().contiguous()) if wplanes else (lambda t: t.to(WEIGHT_DT[dtype]).contiguous())
+        dt = X3W if wplanes else dtype                    # the code the weights are packed for (X3W: ops.Planed packs)
+        # The RMSNorm gain is folded into the packed weights only in the fp32 build.  The bf16 and split builds keep the
+        # checkpoint's bf16 weights as they are and apply the gain to the activations: in the producer's epilogue on the
+        # decode step (csrc/decode.hip), in the kernel for prompt chunks (kgamma).
+        self.unfolded = dtype != F32
+        ks = (lambda g: None) if self.unfolded else (lambda g: g)
+        if h2:                                            # fp16 packs: one plane (bf16-representable checkpoint) or hi + lo
+            pk = lambda w, g=None, ih=0: ops.pack_skinny_h2(w, planes=(2 if wplanes else 1), interleave_half=ih)
+        else:
+            pk = lambda w, g=None, ih=0: ops.pack_skinny(c(w), dtype=dt, kscale=ks(g), interleave_half=ih)
+        self.n_layers = len({k.split(".")[4] for k in sd if k.startswith(prefix + ".layers.")})
+        self.H = sd[prefix + ".norm.weight"].shape[0]
+        self.I = sd[prefix + ".layers.0.mlp.gate_proj.weight"].shape[0]
+        self.layers, self.pf_layers = [], []
+        for l in range(self.n_layers):
+            p = f"{prefix}.layers.{l}"
+            a = p + ".self_attn"
+            wqkv = torch.cat([f(a + ".q_proj.weight"), f(a + ".k_proj.weight"), f(a + ".v_proj.weight")], 0)
+            bqkv = torch.cat([f(a + ".q_proj.bias"), f(a + ".k_proj.bias"), f(a + ".v_proj.bias")], 0).contiguous()
+            wgu = torch.cat([f(p + ".mlp.gate_proj.weight"), f(p + ".mlp.up_proj.weight")], 0)
+            g1, g2 = f(p + ".input_layernorm.weight"), f(p + ".post_attention_layernorm.weight")
+            if gemm_packs:
+                # row-major copies for the windowed GEMM (_gemm_layers): many prompt rows at once are an ordinary tall GEMM
+                # over weights read once, not passes of the weight-streaming decode kernels
+                self.pf_layers.append(dict(
+                    wqkv=ops.pack_linear(c(wqkv), dt), wo=ops.pack_linear(c(f(a + ".o_proj.weight")), dt),
+                    wgu=ops.pack_linear(c(wgu), dt), wdown=ops.pack_linear(c(f(p + ".mlp.down_proj.weight")), dt), g1=g1, g2=g2))
+            self.layers.append(dict(wqkv=pk(wqkv, g1), bqkv=bqkv, wo=pk(f(a + ".o_proj.weight")), wgu=pk(wgu, g2, self.I),
+                                    wdown=pk(f(p + ".mlp.down_proj.weight")), g1=g1, g2=g2))
+            del wqkv, wgu
+        self.norm_w = f(prefix + ".norm.weight")
+        self.embed_tokens = f(prefix + ".embed_tokens.weight")
+        if "llm_decoder.weight" in sd:
+            self.wdec = pk(f("llm_decoder.weight"), self.norm_w)
+            self.bdec = f("llm_decoder.bias")
+            self.speech_emb = f("speech_embedding.weight")
+            self.llm_emb = f("llm_embedding.weight")
+        else:                                              # backbone only (Qwen2Encoder.forward_one_step)
+            self.wdec = self.bdec = self.speech_emb = self.llm_emb = None
+        # HF Qwen2RotaryEmbedding inv_freq (modeling_qwen2.py: 1 / theta^(arange(0,d,2)/d)), computed like HF in fp32
+        self.inv_freq = (1.0 / (rope_theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).float() / head_dim))).to(self.dev)
+        # cos/sin per position exactly as HF computes them (fp32 outer product, then cos/sin): [max_ctx][cos 32 | sin 32]
+        # one capacity for the KV pages, the RoPE table, the token history and every guard: whole pages
+        self.max_pages = (max_ctx + page - 1) // page
+        self.max_out = self.max_pages * page
+        ang = torch.arange(self.max_out, dtype=torch.float32)[:, None] * self.inv_freq.cpu()[None, :]
+        self.rope_tab = torch.cat([ang.cos(), ang.sin()], dim=1).contiguous().to(self.dev)
+        # paged KV cache: [layers][pages][Hkv][page][D]; pages are handed out by a free-list allocator, a slot's block
+        # table row lists the pages of the sequence it currently runs (idle slots point at the scratch page)
+        npages = max_batch * self.max_pages if kv_pages is None else int(kv_pages)
+        self.trash_page = npages                  # scratch page: idle slots append their (ignored) KV here
+        self.kc = torch.zeros(self.n_layers, npages + 1, kv_heads, page, head_dim, dtype=self.tdt, device=self.dev)
+        self.vc = torch.zeros_like(self.kc)
+        self.pages = PageAllocator(npages)
+
+
 class LlmEngine:
     # decode attention: batches of at least this many sequences use the GQA-shared kernel (one workgroup per kv head serving
     # its 7 query heads), smaller ones the per-head kernel (more workgroups for the few sequences there are)
@@ -65,111 +140,42 @@ class LlmEngine:
 
     def __init__(self, sd: Dict[str, torch.Tensor], dtype=BF16, device="cuda", max_batch=1, max_ctx=2048, page=16,
                  heads=14, kv_heads=2, head_dim=64, rope_theta=1e6, eps=1e-6, speech_token_size=6561, use_graphs=True,
-                 prefix="llm.model.model", share_from=None, kv_pages=None, wplanes=False, lm_planes=None):
+                 prefix="llm.model.model", share_from=None, kv_pages=None, wplanes=False, lm_planes=None, decode_on=None,
+                 prompt_on=None):
         """wplanes (split build X3 only): every projection weight is carried as THREE bf16 planes hi + mid + lo = the checkpoint's
         fp32 value (MMX_X3W: csrc/decode.hip for the decode step, csrc/gemm.hip for the prompt pass) instead of being rounded to
         bf16 - for checkpoints whose weights are not bf16-representable (the reference loads an fp32 llm.pt, cli/model.py:67-75).
-        Costs 3 x the weight bytes and 2 x the MFMAs of the plain split build."""
-        self.dtype, self.tdt, self.dev = dtype, TORCH_DT[dtype], torch.device(device)
-        self.wplanes = (dtype == X3 and ops.resolve_wplanes(wplanes, (v for k, v in sd.items() if v.dim() >= 2 and ("proj" in k or k == "llm_decoder.weight")))) \
-            if share_from is None else share_from.wplanes
-        planes = (lm_planes or self.lm_planes) if share_from is None else ("f16x2" if share_from.h2 else "bf16x3")
-        assert planes in ("f16x2", "bf16x3")
-        self.h2 = dtype == X3 and planes == "f16x2" and self.use_v2
-        self.ddt = H2 if self.h2 else dtype               # dtype code of the decode-step kernels (csrc/decode.hip)
-        if self.wplanes and not self.h2:                  # three bf16 weight planes in registers: one output tile per workgroup
-            self.v2_cfg = dict(qkv=(1, 1), o=(1, 1), gu=(1, 1), down=(1, 8), head=(1, 1))
-        self.split = is_split(dtype)                      # bf16 weights, fp32 activations split inside the MFMA products
-        self.Hq, self.Hkv, self.D, self.eps = heads, kv_heads, head_dim, eps
-        self.page, self.use_graphs = page, use_graphs
-        self.eos = speech_token_size
-        self.V = speech_token_size + 3
-        dt = dtype
+        Costs 3 x the weight bytes and 2 x the MFMAs of the plain split build.
+        share_from: a second engine of a different batch size over the SAME LmModel - packed weights and paged KV cache - as
+        that engine (used to continue a partly finished batch at a smaller, cheaper batch size: see compact_from).
+        decode_on / prompt_on: the kernel family of the decode step and of prompt rows (_dispatch; None = what the build and the
+        batch size make best).  A combination whose packs no kernel can read raises ValueError."""
         if share_from is not None:
-            # a second engine of a different batch size over the SAME packed weights and the SAME paged KV cache
-            # (used to continue a partly finished batch at a smaller, cheaper batch size: see compact_from)
-            o = share_from
-            for k in ("n_layers", "H", "I", "layers", "wdec", "bdec", "embed_tokens", "speech_emb", "llm_emb", "inv_freq",
-                      "rope_tab", "kc", "vc", "max_pages", "max_out", "trash_page", "pf_layers", "norm_w", "pages", "unfolded"):
-                setattr(self, k, getattr(o, k))
-            self.B = max_batch
-            self.block_table = torch.full((self.B, self.max_pages), self.trash_page, dtype=torch.int32, device=self.dev)
-            self.slot_pages = [[] for _ in range(self.B)]
-            self._alloc_state()
-            return
-        f = lambda k: sd[k].detach().to(self.dev, torch.float32).contiguous()
-        c = (lambda t: t.float().contiguous()) if self.wplanes else (lambda t: t.to(WEIGHT_DT[dtype]).contiguous())
-        if self.wplanes:
-            dt = X3W                                      # the code the weights are packed for (ops.Planed packs)
-        # The RMSNorm gain is folded into the packed weights only in the fp32 build.  The bf16 and split builds keep the
-        # checkpoint's bf16 weights as they are and apply the gain to the activations: in the producer's epilogue on the
-        # decode step (csrc/decode.hip), in the kernel for prompt chunks (kgamma).
-        self.unfolded = dtype != F32
-        ks = (lambda g: None) if self.unfolded else (lambda g: g)
-        self.n_layers = len({k.split(".")[4] for k in sd if k.startswith(prefix + ".layers.")})
-        self.H = sd[prefix + ".norm.weight"].shape[0]
-        self.I = sd[prefix + ".layers.0.mlp.gate_proj.weight"].shape[0]
-        self.layers, self.pf_layers = [], []
-        for l in range(self.n_layers):
-            p = f"{prefix}.layers.{l}"
-            a = p + ".self_attn"
-            wqkv = torch.cat([f(a + ".q_proj.weight"), f(a + ".k_proj.weight"), f(a + ".v_proj.weight")], 0)
-            bqkv = torch.cat([f(a + ".q_proj.bias"), f(a + ".k_proj.bias"), f(a + ".v_proj.bias")], 0).contiguous()
-            wgu = torch.cat([f(p + ".mlp.gate_proj.weight"), f(p + ".mlp.up_proj.weight")], 0)
-            if max_batch >= 4 or self.wplanes or self.h2:
-                # row-major copies for the batched prompt pass (_prefill_batch): many prompts at once are an ordinary
-                # tall GEMM over weights read once, not max_batch passes of the weight-streaming decode kernels
-                self.pf_layers.append(dict(
-                    wqkv=ops.pack_linear(c(wqkv), dt), wo=ops.pack_linear(c(f(a + ".o_proj.weight")), dt),
-                    wgu=ops.pack_linear(c(wgu), dt), wdown=ops.pack_linear(c(f(p + ".mlp.down_proj.weight")), dt),
-                    g1=f(p + ".input_layernorm.weight"), g2=f(p + ".post_attention_layernorm.weight")))
-            if self.h2:                                   # fp16 packs (w * 2^8): one plane (bf16-representable checkpoint) or hi + lo
-                pk = lambda w, ih=0: ops.pack_skinny_h2(w, planes=(2 if self.wplanes else 1), interleave_half=ih)
-                self.layers.append(dict(wqkv=pk(wqkv), bqkv=bqkv, wo=pk(f(a + ".o_proj.weight")), wgu=pk(wgu, self.I),
-                                        wdown=pk(f(p + ".mlp.down_proj.weight")),
-                                        g1=f(p + ".input_layernorm.weight"), g2=f(p + ".post_attention_layernorm.weight")))
-                del wqkv, wgu
-                continue
-            self.layers.append(dict(
-                wqkv=ops.pack_skinny(c(wqkv), dtype=dt, kscale=ks(f(p + ".input_layernorm.weight"))), bqkv=bqkv,
-                wo=ops.pack_skinny(c(f(a + ".o_proj.weight")), dtype=dt),
-                wgu=ops.pack_skinny(c(wgu), dtype=dt, kscale=ks(f(p + ".post_attention_layernorm.weight")), interleave_half=self.I),
-                wdown=ops.pack_skinny(c(f(p + ".mlp.down_proj.weight")), dtype=dt),
-                g1=f(p + ".input_layernorm.weight"), g2=f(p + ".post_attention_layernorm.weight")))
-            del wqkv, wgu
-        self.norm_w = f(prefix + ".norm.weight")
-        self.embed_tokens = f(prefix + ".embed_tokens.weight")
-        if "llm_decoder.weight" in sd:
-            self.wdec = ops.pack_skinny_h2(f("llm_decoder.weight"), planes=(2 if self.wplanes else 1)) if self.h2 else \
-                ops.pack_skinny(c(f("llm_decoder.weight")), dtype=dt, kscale=ks(self.norm_w))
-            self.bdec = f("llm_decoder.bias")
-            self.speech_emb = f("speech_embedding.weight")
-            self.llm_emb = f("llm_embedding.weight")
-        else:                                              # backbone only (Qwen2Encoder.forward_one_step)
-            self.wdec = self.bdec = self.speech_emb = self.llm_emb = None
-        # HF Qwen2RotaryEmbedding inv_freq (modeling_qwen2.py: 1 / theta^(arange(0,d,2)/d)), computed like HF in fp32
-        self.inv_freq = (1.0 / (rope_theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).float() / head_dim))).to(self.dev)
-        # cos/sin per position exactly as HF computes them (fp32 outer product, then cos/sin): [max_ctx][cos 32 | sin 32]
-        # one capacity for the KV pages, the RoPE table, the token history and every guard: whole pages
-        self.max_pages = (max_ctx + page - 1) // page
-        max_ctx = self.max_pages * page
-        ang = torch.arange(max_ctx, dtype=torch.float32)[:, None] * self.inv_freq.cpu()[None, :]
-        self.rope_tab = torch.cat([ang.cos(), ang.sin()], dim=1).contiguous().to(self.dev)
-        # paged KV cache: [layers][pages][Hkv][page][D]; pages are handed out by a free-list allocator, a slot's block
-        # table row lists the pages of the sequence it currently runs (idle slots point at the scratch page)
-        self.B = max_batch
-        npages = self.B * self.max_pages if kv_pages is None else int(kv_pages)
-        self.trash_page = npages                  # scratch page: idle slots append their (ignored) KV here
-        self.kc = torch.zeros(self.n_layers, npages + 1, kv_heads, page, head_dim, dtype=self.tdt, device=self.dev)
-        self.vc = torch.zeros_like(self.kc)
-        self.pages = PageAllocator(npages)
-        self.block_table = torch.full((self.B, self.max_pages), self.trash_page, dtype=torch.int32, device=self.dev)
-        self.slot_pages = [[] for _ in range(self.B)]
-        self.max_out = max_ctx
-        self._alloc_state()
-
-    def _alloc_state(self):
+            m, v2 = share_from.model, share_from.v2 if decode_on is None else decode_on == "planes"
+            dtype, h2, wplanes, gemm_packs = m.dtype, m.h2, m.wplanes, bool(m.pf_layers)
+        else:
+            wplanes = dtype == X3 and ops.resolve_wplanes(wplanes, (v for k, v in sd.items() if v.dim() >= 2 and ("proj" in k or k == "llm_decoder.weight")))
+            planes = lm_planes or self.lm_planes
+            if planes not in ("f16x2", "bf16x3"):
+                raise ValueError(f"lm_planes {planes!r}: 'f16x2' or 'bf16x3'")
+            v2, gemm_packs = self.use_v2 if decode_on is None else decode_on == "planes", True
+            h2 = dtype == X3 and planes == "f16x2" and v2  # (the round-2 kernel takes the bf16 packs)
+        self.decode_on, self.prompt_on = self._dispatch(dtype, h2, wplanes, v2, max_batch, decode_on, prompt_on, gemm_packs)
+        if share_from is None:
+            m = LmModel(sd, dtype, device, max_batch, max_ctx, page, heads, kv_heads, head_dim, rope_theta, eps, speech_token_size,
+                        prefix, kv_pages, wplanes, h2, gemm_packs=self.prompt_on != "skinny")
+        self.model, self.B, self.use_graphs, self.v2 = m, max_batch, use_graphs, v2      # (v2: decode step asked for on csrc/decode.hip)
+        # the model's fields that tests, tools, bench.py and the drop-in read from an engine, under the names they always had
+        self.dtype, self.tdt, self.ddt, self.dev, self.h2, self.wplanes = m.dtype, m.tdt, m.ddt, m.dev, m.h2, m.wplanes
+        self.n_layers, self.H, self.I, self.Hq, self.Hkv, self.D, self.eps = m.n_layers, m.H, m.I, m.Hq, m.Hkv, m.D, m.eps
+        self.page, self.max_pages, self.max_out, self.eos, self.V = m.page, m.max_pages, m.max_out, m.eos, m.V
+        self.layers, self.llm_emb, self.speech_emb, self.embed_tokens = m.layers, m.llm_emb, m.speech_emb, m.embed_tokens
+        self.kc, self.vc, self.pages = m.kc, m.vc, m.pages
+        if m.wplanes and not m.h2:                        # three bf16 weight planes in registers: one output tile per workgroup
+            self.v2_cfg = dict(qkv=(1, 1), o=(1, 1), gu=(1, 1), down=(1, 8), head=(1, 1))
         B = self.B
+        self.block_table = torch.full((B, m.max_pages), m.trash_page, dtype=torch.int32, device=self.dev)
+        self.slot_pages = [[] for _ in range(B)]
         self.state = torch.zeros(8, B, dtype=torch.int32, device=self.dev)
         self.out_tokens = torch.zeros(B, self.max_out, dtype=torch.int32, device=self.dev)
         self.sampled = torch.full((B, self.max_out), -1, dtype=torch.int32, device=self.dev)
@@ -178,58 +184,82 @@ class LlmEngine:
         self.h = torch.zeros(B, self.H, device=self.dev)            # residual stream of the step
         # its compute-dtype copy; at batch > 8 the decode step keeps it (and every other GEMM input) in the packed
         # MFMA-fragment order of include/mmx_hip.h (whole 16-row tiles)
-        self.packed = B >= 4 and not self.unfolded
+        self.packed = B >= 4 and not m.unfolded
         self.h_act = torch.zeros(ops.packed_rows(B), self.H, dtype=self.tdt, device=self.dev)
         self.logits = torch.zeros(B, self.V, device=self.dev)
         self.logp = torch.zeros(B, self.V, device=self.dev)
-        self.want_logp = False
         # the engine's default sampler (config.yaml:46-50): what a sequence gets that is started without one of its own
-        self.seed = 0
+        self.seed, self.want_logp = 0, False
         self.mode, self.top_p, self.top_k, self.win_size, self.tau_r = 0, 0.8, 25, 10, 0.1
         # the sampler table the kernel reads (field-major, one column per slot) and its host mirror
         self._samp_host = [self._sampler_fields(None, None) for _ in range(B)]
         self.samp = torch.tensor([ops.sampler_column(**f) for f in self._samp_host], dtype=torch.int32).t().contiguous().to(self.dev)
-        self._decode = None
+        self._decode, self._graph_key = None, None
         self.reserve_ahead = 1 << 30               # start(): rows reserved past the prompt (default: the whole max_len)
+
+    @staticmethod
+    def _dispatch(dtype, h2, wplanes, v2, B, decode_on, prompt_on, gemm_packs):
+        """-> (decode_on, prompt_on): the kernel family that serves B sequences over packs of (dtype, h2, wplanes).
+        decode_on, the decode step: "planes" = csrc/decode.hip on split-plane activations (bf16 and split builds, <= 32
+        sequences, v2: asked for), else "skinny" = mmx_skinny_gemm, the round-2 projection kernel.
+        prompt_on, prompt rows: "gemm" = the windowed GEMM; "skinny" = mmx_skinny_gemm chunks of <= 64 rows over the decode
+        packs; "gemm-batch" (>= 4 slots) = the prompts of a start() as one tall GEMM pass, weights read once for all of them,
+        and rows entering a single slot (admit, feed, forward_rows) as skinny chunks.
+        fp16 and weight-plane packs (h2 / wplanes) are read by csrc/decode.hip and, row-major, by the windowed GEMM only:
+        whatever else is asked of them raises ValueError, as does a family named by keyword that cannot serve.
+        gemm_packs: the model has, or will get, the row-major copies."""
+        planes_only = h2 or wplanes
+        packs = ("fp16" if h2 else "bf16") + (" weight-plane" if wplanes else "") + " decode packs"
+        decode = "planes" if v2 and dtype != F32 and B <= 32 else "skinny"
+        if decode_on not in (None, decode):
+            raise ValueError(f"decode_on={decode_on!r}: 'planes' (csrc/decode.hip) serves the bf16 and split builds up to 32 sequences, "
+                             f"'skinny' (mmx_skinny_gemm) the rest; this is dtype {dtype} at max_batch {B}")
+        if planes_only and decode != "planes":
+            raise ValueError(f"{packs} are read by csrc/decode.hip only, which does not serve " +
+                             (f"max_batch {B} > 32" if v2 else "the round-2 kernel (use_v2 = False / decode_on='skinny')"))
+        ok = ("gemm",) if planes_only else ("gemm", "gemm-batch", "skinny") if gemm_packs else ("skinny",)
+        if prompt_on not in (None,) + ok:
+            raise ValueError(f"prompt_on={prompt_on!r}: {packs}" + ("" if gemm_packs else ", shared model without row-major copies,") + f" take {ok}")
+        return decode, prompt_on or ("gemm" if planes_only else "gemm-batch" if B >= 4 and gemm_packs else "skinny")
 
     # ------------------------------------------------------------------ one transformer pass over `rows` tokens/seq
     def _layers(self, h, ha, B, rows, pos, block_table, packed=False):
-        """h fp32 [B*rows, H] residual stream (in place) and ha, its compute-dtype copy (kept in sync by the
-        residual epilogues: it is the A operand of the next RMSNorm-folded projection).
+        """The layers on mmx_skinny_gemm (prompt chunks; the decode step where decode_on is "skinny").
+        h fp32 [B*rows, H] residual stream (in place) and ha, its compute-dtype copy (kept in sync by the residual epilogues: it
+        is the A operand of the next RMSNorm-folded projection; unused in the split build, whose GEMM inputs are the fp32
+        tensors themselves).  bf16 and split builds: the RMSNorm gains ride as kgamma on the fp32 residual stream.
         pos int32 [B] device, block_table [B, max_pages].
         packed (decode step, batch > 8): ha / att / act live in the packed fragment order; the first projection
         reads the fp32 residual stream itself (row-major), so no packing pass is needed for the input embedding."""
-        dt, H, I = self.dtype, self.H, self.I
+        m = self.model
+        dt, H, I = m.dtype, m.H, m.I
         n = B * rows
         assert n <= 64 and not (packed and rows != 1)
-        if self.split:
-            return self._layers_split(h, B, rows, pos, block_table)
         nr = ops.packed_rows(n) if packed else n
-        qkv = torch.empty(n, (self.Hq + 2 * self.Hkv) * self.D, device=self.dev)
-        q = torch.empty(n, self.Hq * self.D, dtype=self.tdt, device=self.dev)
-        att = torch.empty(nr, self.Hq * self.D, dtype=self.tdt, device=self.dev)
-        act = torch.empty(nr, I, dtype=self.tdt, device=self.dev)
-        pk = packed
-        kg = (lambda g: g) if self.unfolded else (lambda g: None)     # bf16 build: gain applied to the fp32 residual stream in-kernel
-        for l, w in enumerate(self.layers):
-            first = (packed and l == 0) or self.unfolded
+        qkv = torch.empty(n, (m.Hq + 2 * m.Hkv) * m.D, device=self.dev)
+        q = torch.empty(n, m.Hq * m.D, dtype=m.tdt, device=self.dev)
+        att = torch.empty(nr, m.Hq * m.D, dtype=m.tdt, device=self.dev)
+        act = torch.empty(nr, I, dtype=m.tdt, device=self.dev)
+        kg = (lambda g: g) if m.unfolded else (lambda g: None)
+        res = dict(out_f32=h) if m.split else dict(out_f32=h, out_act=ha)      # the residual epilogues' outputs
+        gu = dict(out_f32=act) if m.split else dict(out_act=act)               # SwiGLU product in the activation dtype
+        for l, w in enumerate(m.layers):
+            first = (packed and l == 0) or m.unfolded
             ops.skinny_gemm(h if first else ha, w["wqkv"], B=n, K=H, N=qkv.shape[1], dtype=dt, bias=w["bqkv"], rs=True,
-                            eps=self.eps, epi=0, out_f32=qkv, x_packed=pk and not first, kgamma=kg(w["g1"]))
+                            eps=m.eps, epi=0, out_f32=qkv, x_packed=packed and not first, kgamma=kg(w["g1"]))
             if rows == 1:
-                ops.decode_attn(qkv, self.inv_freq, pos, self.kc[l], self.vc[l], block_table, att, B=B, Hq=self.Hq,
-                                Hkv=self.Hkv, page=self.page, dtype=dt, rope_tab=self.rope_tab, out_packed=pk,
-                                per_head=B < self.gqa_min_batch)
+                ops.decode_attn(qkv, m.inv_freq, pos, m.kc[l], m.vc[l], block_table, att, B=B, Hq=m.Hq,
+                                Hkv=m.Hkv, page=m.page, dtype=dt, rope_tab=m.rope_tab, out_packed=packed,
+                                per_head=m.split or B < self.gqa_min_batch)
             else:
-                ops.rope_kv_store(qkv, self.inv_freq, pos, q, self.kc[l], self.vc[l], block_table, B=B, rows=rows,
-                                  Hq=self.Hq, Hkv=self.Hkv, page=self.page, dtype=dt)
-                ops.paged_attn(q, pos, self.kc[l], self.vc[l], block_table, att, B=B, rows=rows, Hq=self.Hq,
-                               Hkv=self.Hkv, page=self.page, dtype=dt)
-            ops.skinny_gemm(att, w["wo"], B=n, K=self.Hq * self.D, N=H, dtype=dt, epi=2, out_f32=h, out_act=ha,
-                            x_packed=pk, out_packed=pk)
-            ops.skinny_gemm(h if self.unfolded else ha, w["wgu"], B=n, K=H, N=I, dtype=dt, rs=True, eps=self.eps, epi=1, out_act=act,
-                            x_packed=pk, out_packed=pk, kgamma=kg(w["g2"]))
-            ops.skinny_gemm(act, w["wdown"], B=n, K=I, N=H, dtype=dt, epi=2, out_f32=h, out_act=ha,
-                            x_packed=pk, out_packed=pk)
+                ops.rope_kv_store(qkv, m.inv_freq, pos, q, m.kc[l], m.vc[l], block_table, B=B, rows=rows,
+                                  Hq=m.Hq, Hkv=m.Hkv, page=m.page, dtype=dt)
+                ops.paged_attn(q, pos, m.kc[l], m.vc[l], block_table, att, B=B, rows=rows, Hq=m.Hq,
+                               Hkv=m.Hkv, page=m.page, dtype=dt)
+            ops.skinny_gemm(att, w["wo"], B=n, K=m.Hq * m.D, N=H, dtype=dt, epi=2, x_packed=packed, out_packed=packed, **res)
+            ops.skinny_gemm(h if m.unfolded else ha, w["wgu"], B=n, K=H, N=I, dtype=dt, rs=True, eps=m.eps, epi=1,
+                            x_packed=packed, out_packed=packed, kgamma=kg(w["g2"]), **gu)
+            ops.skinny_gemm(act, w["wdown"], B=n, K=I, N=H, dtype=dt, epi=2, x_packed=packed, out_packed=packed, **res)
 
     # decode-step projections of the split build (csrc/decode.hip): (output tiles per workgroup, k slices across workgroups)
     v2_cfg = dict(qkv=(1, 1), o=(1, 1), gu=(2, 1), down=(2, 8), head=(2, 1))
@@ -238,107 +268,87 @@ class LlmEngine:
         """Static buffers of the split-plane decode step (csrc/decode.hip): activation planes, sum-of-squares tables (zeroed:
         unused tile slots must read 0), partial tiles and tickets of the down projection's cross-workgroup k split."""
         if not hasattr(self, "_v2"):
-            H, I, R = self.H, self.I, ops.packed_rows(self.B)
-            NQ = (self.Hq + 2 * self.Hkv) * self.D
-            bf = lambda K: torch.zeros((2 if self.h2 else 3) if self.split else 1, R * K, dtype=torch.bfloat16, device=self.dev)
+            m = self.model
+            H, I, R = m.H, m.I, ops.packed_rows(self.B)
+            NQ = (m.Hq + 2 * m.Hkv) * m.D
+            bf = lambda K: torch.zeros((2 if m.h2 else 3) if m.split else 1, R * K, dtype=torch.bfloat16, device=self.dev)
             J = self.v2_cfg["down"][1]
-            self._v2 = dict(qkv=torch.empty(self.B, NQ, device=self.dev), xs_a=bf(H), xs_b=bf(H), xs_att=bf(self.Hq * self.D), xs_act=bf(I),
+            self._v2 = dict(qkv=torch.empty(self.B, NQ, device=self.dev), xs_a=bf(H), xs_b=bf(H), xs_att=bf(m.Hq * m.D), xs_act=bf(I),
                             ssq_a=torch.zeros(32, ops.SSQ_SLOTS, device=self.dev), ssq_b=torch.zeros(32, ops.SSQ_SLOTS, device=self.dev),
                             part=torch.empty(J * ((H + 15) // 16) * (R // 4) * 64, device=self.dev),
                             tickets=torch.zeros((H + 15) // 16, dtype=torch.int32, device=self.dev))
         return self._v2
 
+    def _prefetch(self, l=None):
+        """The decode step's weight prefetch (LlmEngine.prefetch workgroups; 0 = off, the default: a measured negative, kept for
+        bench.py --lm-prefetch).  l: fork - a side stream touches the packs of layer l + 1 (the head's after the last layer)
+        while layer l computes; None: join - the side stream's last launch belongs to this step."""
+        if not int(self.prefetch):
+            return
+        if not hasattr(self, "_pf_side"):
+            self._pf_side = torch.cuda.Stream(device=self.dev)
+            self._pf_sink = torch.zeros(4, dtype=torch.int32, device=self.dev)
+        layers, ev = self.model.layers, torch.cuda.Event()
+        src, dst = (torch.cuda.current_stream(), self._pf_side) if l is not None else (self._pf_side, torch.cuda.current_stream())
+        ev.record(src)
+        dst.wait_event(ev)
+        if l is not None:
+            with torch.cuda.stream(self._pf_side):
+                ops.prefetch4([layers[l + 1][k] for k in ("wqkv", "wo", "wgu", "wdown")] if l + 1 < len(layers) else [self.model.wdec],
+                              self._pf_sink, int(self.prefetch))
+
     def _layers_split_decode(self, x_in, h, B, pos, block_table):
-        """One decode step of the split build on split-plane activations (B <= 32 sequences): one prep launch, then 5
-        launches per layer.  x_in -> h (residual stream, fp32) and the planes of h * gamma; every projection's epilogue
-        writes the planes (and the RMSNorm partial sums) its consumer reads.  Leaves the planes of h * norm_w and the sums
-        of squares of h in xs_a / ssq_a for the head."""
-        dt, H, I, c, S = self.ddt, self.H, self.I, self.v2_cfg, self._planes()
-        NQ = (self.Hq + 2 * self.Hkv) * self.D
+        """One decode step of the bf16 and split builds on split-plane activations (csrc/decode.hip, B <= 32 sequences): one
+        prep launch, then 5 launches per layer.  x_in -> h (residual stream, fp32) and the planes of h * gamma; every
+        projection's epilogue writes the planes (and the RMSNorm partial sums) its consumer reads.  Leaves the planes of
+        h * norm_w and the sums of squares of h in xs_a / ssq_a for the head."""
+        m = self.model
+        dt, H, I, c, S = m.ddt, m.H, m.I, self.v2_cfg, self._planes()
+        NQ = (m.Hq + 2 * m.Hkv) * m.D
         qkv = S["qkv"][:B]
-        ops.decode_prep(x_in, S["xs_a"], S["ssq_a"], B=B, K=H, gamma=self.layers[0]["g1"], h=h, dtype=dt)
-        pf = int(self.prefetch)
-        if pf:
-            if not hasattr(self, "_pf_side"):
-                self._pf_side = torch.cuda.Stream(device=self.dev)
-                self._pf_sink = torch.zeros(4, dtype=torch.int32, device=self.dev)
-            cur, side = torch.cuda.current_stream(), self._pf_side
-        for l, w in enumerate(self.layers):
-            if pf:                                        # fork: the next layer's weights (the head's after the last layer)
-                nxt = self.layers[l + 1] if l + 1 < len(self.layers) else None
-                ev = torch.cuda.Event()
-                ev.record(cur)
-                side.wait_event(ev)
-                with torch.cuda.stream(side):
-                    ops.prefetch4([nxt["wqkv"], nxt["wo"], nxt["wgu"], nxt["wdown"]] if nxt is not None else [self.wdec], self._pf_sink, pf)
-            g_next = self.layers[l + 1]["g1"] if l + 1 < len(self.layers) else self.norm_w
-            ops.skinny2(S["xs_a"], w["wqkv"], B=B, K=H, N=NQ, dtype=dt, bias=w["bqkv"], ssq_in=S["ssq_a"], eps=self.eps, epi=0, out=qkv,
+        ops.decode_prep(x_in, S["xs_a"], S["ssq_a"], B=B, K=H, gamma=m.layers[0]["g1"], h=h, dtype=dt)
+        for l, w in enumerate(m.layers):
+            self._prefetch(l)
+            g_next = m.layers[l + 1]["g1"] if l + 1 < len(m.layers) else m.norm_w
+            ops.skinny2(S["xs_a"], w["wqkv"], B=B, K=H, N=NQ, dtype=dt, bias=w["bqkv"], ssq_in=S["ssq_a"], eps=m.eps, epi=0, out=qkv,
                         tiles_per_wg=c["qkv"][0])
             # (bf16 build: one plane = the packed A-fragment order the attention kernels already write)
-            ops.decode_attn(qkv, self.inv_freq, pos, self.kc[l], self.vc[l], block_table, S["xs_att"], B=B, Hq=self.Hq,
-                            Hkv=self.Hkv, page=self.page, dtype=self.dtype, rope_tab=self.rope_tab, per_head=(self.split or B < self.gqa_min_batch),
-                            out_split=("f16" if self.h2 else self.split), out_packed=not self.split)
-            ops.skinny2(S["xs_att"], w["wo"], B=B, K=self.Hq * self.D, N=H, dtype=dt, epi=2, out=h, xs_out=S["xs_b"],
+            ops.decode_attn(qkv, m.inv_freq, pos, m.kc[l], m.vc[l], block_table, S["xs_att"], B=B, Hq=m.Hq,
+                            Hkv=m.Hkv, page=m.page, dtype=m.dtype, rope_tab=m.rope_tab, per_head=(m.split or B < self.gqa_min_batch),
+                            out_split=("f16" if m.h2 else m.split), out_packed=not m.split)
+            ops.skinny2(S["xs_att"], w["wo"], B=B, K=m.Hq * m.D, N=H, dtype=dt, epi=2, out=h, xs_out=S["xs_b"],
                         gamma_next=w["g2"], ssq_out=S["ssq_b"], tiles_per_wg=c["o"][0])
-            ops.skinny2(S["xs_b"], w["wgu"], B=B, K=H, N=I, dtype=dt, ssq_in=S["ssq_b"], eps=self.eps, epi=1, xs_out=S["xs_act"],
+            ops.skinny2(S["xs_b"], w["wgu"], B=B, K=H, N=I, dtype=dt, ssq_in=S["ssq_b"], eps=m.eps, epi=1, xs_out=S["xs_act"],
                         tiles_per_wg=c["gu"][0])
             ops.skinny2(S["xs_act"], w["wdown"], B=B, K=I, N=H, dtype=dt, epi=2, out=h, xs_out=S["xs_a"], gamma_next=g_next,
                         ssq_out=S["ssq_a"], tiles_per_wg=c["down"][0], ksplit=c["down"][1], part=S["part"], tickets=S["tickets"])
-        if pf:                                            # join: the side stream's last launch belongs to this step
-            ev = torch.cuda.Event()
-            ev.record(side)
-            cur.wait_event(ev)
-
-    def _layers_split(self, h, B, rows, pos, block_table):
-        """The split build of _layers: every GEMM input is the fp32 tensor itself (row-major), the RMSNorm gains ride as
-        kgamma, all intermediates are fp32."""
-        dt, H, I = self.dtype, self.H, self.I
-        n = B * rows
-        qkv = torch.empty(n, (self.Hq + 2 * self.Hkv) * self.D, device=self.dev)
-        q = torch.empty(n, self.Hq * self.D, device=self.dev)
-        att = torch.empty(n, self.Hq * self.D, device=self.dev)
-        act = torch.empty(n, I, device=self.dev)
-        for l, w in enumerate(self.layers):
-            ops.skinny_gemm(h, w["wqkv"], B=n, K=H, N=qkv.shape[1], dtype=dt, bias=w["bqkv"], rs=True, eps=self.eps, epi=0,
-                            out_f32=qkv, kgamma=w["g1"])
-            if rows == 1:
-                ops.decode_attn(qkv, self.inv_freq, pos, self.kc[l], self.vc[l], block_table, att, B=B, Hq=self.Hq,
-                                Hkv=self.Hkv, page=self.page, dtype=dt, rope_tab=self.rope_tab, per_head=True)
-            else:
-                ops.rope_kv_store(qkv, self.inv_freq, pos, q, self.kc[l], self.vc[l], block_table, B=B, rows=rows,
-                                  Hq=self.Hq, Hkv=self.Hkv, page=self.page, dtype=dt)
-                ops.paged_attn(q, pos, self.kc[l], self.vc[l], block_table, att, B=B, rows=rows, Hq=self.Hq,
-                               Hkv=self.Hkv, page=self.page, dtype=dt)
-            ops.skinny_gemm(att, w["wo"], B=n, K=self.Hq * self.D, N=H, dtype=dt, epi=2, out_f32=h)
-            ops.skinny_gemm(h, w["wgu"], B=n, K=H, N=I, dtype=dt, rs=True, eps=self.eps, epi=1, out_f32=act, kgamma=w["g2"])
-            ops.skinny_gemm(act, w["wdown"], B=n, K=I, N=H, dtype=dt, epi=2, out_f32=h)
+        self._prefetch(None)
 
     def _tail(self, B, packed=False, planes_ready=False):
         """final RMSNorm (folded) + llm_decoder + log_softmax + sampler + loop bookkeeping for all B sequences.
-        planes_ready (split build): xs_a / ssq_a already hold the planes of h * norm_w (the decode step's last projection
-        wrote them); otherwise they are made from self.h first."""
-        if self.unfolded and B <= 32 and self.use_v2:
+        planes_ready (decode step on csrc/decode.hip): xs_a / ssq_a already hold the planes of h * norm_w (the step's last
+        projection wrote them); otherwise they are made from self.h first."""
+        m = self.model
+        if self.decode_on == "planes":
             S = self._planes()
             if not planes_ready:
-                ops.decode_prep(self.h, S["xs_a"], S["ssq_a"], B=B, K=self.H, gamma=self.norm_w, dtype=self.ddt)
-            ops.skinny2(S["xs_a"], self.wdec, B=B, K=self.H, N=self.V, dtype=self.ddt, bias=self.bdec, ssq_in=S["ssq_a"],
-                        eps=self.eps, epi=0, out=self.logits, tiles_per_wg=self.v2_cfg["head"][0])
-        elif self.unfolded:
-            ops.skinny_gemm(self.h, self.wdec, B=B, K=self.H, N=self.V, dtype=self.dtype, bias=self.bdec, rs=True,
-                            eps=self.eps, epi=0, out_f32=self.logits, kgamma=self.norm_w)
-        else:
-            ops.skinny_gemm(self.h_act, self.wdec, B=B, K=self.H, N=self.V, dtype=self.dtype, bias=self.bdec, rs=True,
-                            eps=self.eps, epi=0, out_f32=self.logits, x_packed=packed)
-        ops.sample_step_tab(self.logits, self.state, self.out_tokens, self.speech_emb, self.x_in, self.samp, V=self.V, B=B,
-                            eos_id=self.eos, sampled=self.sampled, forced=self.forced,
+                ops.decode_prep(self.h, S["xs_a"], S["ssq_a"], B=B, K=m.H, gamma=m.norm_w, dtype=m.ddt)
+            ops.skinny2(S["xs_a"], m.wdec, B=B, K=m.H, N=m.V, dtype=m.ddt, bias=m.bdec, ssq_in=S["ssq_a"],
+                        eps=m.eps, epi=0, out=self.logits, tiles_per_wg=self.v2_cfg["head"][0])
+        else:                                             # gain on the fp32 stream (kgamma), or folded into wdec (fp32 build)
+            x, kw = (self.h, dict(kgamma=m.norm_w)) if m.unfolded else (self.h_act, dict(x_packed=packed))
+            ops.skinny_gemm(x, m.wdec, B=B, K=m.H, N=m.V, dtype=m.dtype, bias=m.bdec, rs=True, eps=m.eps, epi=0, out_f32=self.logits, **kw)
+        ops.sample_step_tab(self.logits, self.state, self.out_tokens, m.speech_emb, self.x_in, self.samp, V=m.V, B=B,
+                            eos_id=m.eos, sampled=self.sampled, forced=self.forced,
                             logp_out=(self.logp if self.want_logp else None))
 
     # ------------------------------------------------------------------ per-sequence samplers
     SAMPLER_FIELDS = ("mode", "top_p", "top_k", "win_size", "tau_r", "seed")
 
-    def _sampler_fields(self, sampler, seed):
-        """The engine's default sampler overridden by `sampler` (a dict over SAMPLER_FIELDS, or None) and `seed` (or None)."""
-        f = {k: getattr(self, k) for k in self.SAMPLER_FIELDS}
+    def _sampler_fields(self, sampler, seed, base=None):
+        """`base` (default: the engine's default sampler) overridden by `sampler` (a dict over SAMPLER_FIELDS, or None) and `seed`
+        (or None): an entry of the host mirror.  The one place where the mode becomes what the table holds."""
+        f = dict(base) if base is not None else {k: getattr(self, k) for k in self.SAMPLER_FIELDS}
         if sampler:
             unknown = set(sampler) - set(self.SAMPLER_FIELDS)
             if unknown:
@@ -360,17 +370,17 @@ class LlmEngine:
         """Changes the sampler of one slot: the fields given (mode 0 / "ras", 1 / "nucleus", 2 / "random"; top_k 1..64; win_size
         0..64), the others stay as the slot has them.  Takes effect at the slot's next sampling step, recorded decode graph included:
         the kernel reads the column from device memory (csrc/sampler.hip)."""
-        f = dict(self._samp_host[slot])
-        f.update({k: v for k, v in dict(mode=mode, top_p=top_p, top_k=top_k, win_size=win_size, tau_r=tau_r, seed=seed).items()
-                  if v is not None})
-        f["mode"] = ops.SAMPLER_MODES.get(f["mode"], f["mode"])
-        col = ops.sampler_column(**f)
+        f = self._sampler_fields(dict(mode=mode, top_p=top_p, top_k=top_k, win_size=win_size, tau_r=tau_r, seed=seed), None,
+                                 base=self._samp_host[slot])
+        self._write_sampler(slot, f, ops.sampler_column(**f))
+
+    def _write_sampler(self, slot, f, col):
         self._samp_host[slot] = f
         self.samp[:, slot].copy_(torch.tensor(col, dtype=torch.int32))
 
     def _decode_step(self):
         B = self.B
-        if self.unfolded and B <= 32 and self.use_v2:
+        if self.decode_on == "planes":
             self._layers_split_decode(self.x_in, self.h, B, self.state[ST_POS], self.block_table)
             return self._tail(B, planes_ready=True)
         self.h.copy_(self.x_in)
@@ -399,7 +409,6 @@ class LlmEngine:
 
     def speaker_conditioning(self, sd_linear_w, sd_linear_b, emb192):
         """normalize -> spk_embed_affine_layer (llm.py:184-186 / :650-653): [1,192] -> [1,H] fp32."""
-        import math
         d = emb192.shape[1]
         g = torch.full((d,), 1.0 / math.sqrt(d), device=self.dev)
         en = torch.empty(1, d, dtype=self.tdt, device=self.dev)
@@ -423,7 +432,7 @@ class LlmEngine:
         if self.slot_pages[slot]:
             self.pages.free(self.slot_pages[slot])
             self.slot_pages[slot] = []
-            self.block_table[slot].fill_(self.trash_page)
+            self.block_table[slot].fill_(self.model.trash_page)
 
     def ensure_capacity(self, ahead: int, pos: Optional[List[int]] = None, active: Optional[List[int]] = None):
         """Called by the host loop between decode steps: every active slot must own pages for the next `ahead` rows
@@ -445,19 +454,18 @@ class LlmEngine:
         the shared scratch page.
         sampler / seed: the request's own (see start); None = the engine's attributes."""
         fields = self._sampler_fields(sampler, seed)
-        ops.sampler_column(**fields)                      # a bad sampler is refused before the slot is touched
+        col = ops.sampler_column(**fields)                # a bad sampler is refused before the slot is touched
         L = x.shape[0]
         if L + max_len > self.max_pages * self.page:
             raise RuntimeError("sequence exceeds the KV cache")
         self.release(slot)
         self._set_pages(slot, L + (max_len if ahead is None else min(ahead, max_len)))
         x = x.to(self.dev, torch.float32).contiguous()
-        for c0 in range(0, L - 1, 64):
-            self._prefill_chunk(x[c0:min(L - 1, c0 + 64)], c0, slot)
+        self._prefill(x[:L - 1], 0, slot)
         self.x_in[slot].copy_(x[L - 1])
         st = torch.tensor([L - 1, 0, 0, 0, min_len, max_len, seq_id, 0], dtype=torch.int32)
         self.state[:, slot].copy_(st)
-        self.set_sampler(slot, **fields)
+        self._write_sampler(slot, fields, col)
         self.sampled[slot].fill_(-1)
 
     def start(self, lm_inputs: List[torch.Tensor], min_lens: List[int], max_lens: List[int], seed=0, seq_ids=None,
@@ -488,26 +496,14 @@ class LlmEngine:
             assert x.shape[0] + max_lens[b] <= self.max_pages * self.page, "sequence exceeds the KV cache"
             self.release(b)
             self._set_pages(b, x.shape[0] + min(max_lens[b], self.reserve_ahead))
-        if (B >= 4 or self.wplanes or self.h2) and self.pf_layers:
+        if self.prompt_on != "skinny":
             self._prefill_batch(lm_inputs)
-            lm_inputs = []
-        for b, x in enumerate(lm_inputs):
-            L = x.shape[0]
-            x = x.to(self.dev, torch.float32).contiguous()
-            for c0 in range(0, L, 64):
-                c1 = min(L, c0 + 64)
-                hc, hca = self._prefill_chunk(x[c0:c1], c0, b)
-            self.h[b].copy_(hc[-1])
-            self.h_act[b].copy_(hca[-1])
-            self.state[ST_POS, b] = L - 1                # the sampler's +1 makes it L (= rows in the cache)
+        else:
+            for b, x in enumerate(lm_inputs):
+                self._prefill(x, 0, b, head=True)
+                self.state[ST_POS, b] = x.shape[0] - 1   # the sampler's +1 makes it L (= rows in the cache)
         self._tail(B)
-        if self._decode is None:
-            self._decode = Graphed(self._decode_step, self.use_graphs)
-        elif self._graph_key != (self.forced is None, want_logp):
-            self._decode.release()
-            self._decode = Graphed(self._decode_step, self.use_graphs)      # baked POINTERS changed: re-record
-        # (forced and logp_out are pointer arguments of the sampler launch; seeds and sampler parameters are device data)
-        self._graph_key = (self.forced is None, want_logp)
+        self._fresh_decode_graph()
 
     def _prefill_batch(self, lm_inputs):
         """All prompts in one pass per layer: rows = B x Lmax (shorter prompts are zero padded; a padded row only adds
@@ -515,7 +511,7 @@ class LlmEngine:
         on the windowed GEMM (weights read once for every prompt), RoPE + KV store + causal attention over the paged
         cache, SwiGLU: 9 launches per layer for the whole batch (32 prompts of 50 rows through the decode kernels cost
         ~58 ms of GPU time: the 1 GB of weights was streamed once per prompt)."""
-        B, dt, H, I = self.B, self.dtype, self.H, self.I
+        B, H = self.B, self.H
         Ls = [int(x.shape[0]) for x in lm_inputs]
         Lm = max(Ls)
         R = B * Lm
@@ -534,43 +530,53 @@ class LlmEngine:
         """The layers over B x Lm prompt rows h [B * Lm, H] (fp32, in place) on the windowed GEMM: RMSNorm, projections (weights read
         once for all rows; weight planes when the packs are ops.Planed), RoPE + KV store + causal attention over the paged cache
         from position pos[b], SwiGLU - 9 launches per layer."""
-        dt, H, I = self.dtype, self.H, self.I
+        m = self.model
+        dt, H, I = m.dtype, m.H, m.I
         R = B * Lm
-        a = torch.empty(R, H, dtype=self.tdt, device=self.dev)
-        qkv = torch.empty(R, (self.Hq + 2 * self.Hkv) * self.D, device=self.dev)
-        q = torch.empty(R, self.Hq * self.D, dtype=self.tdt, device=self.dev)
-        att = torch.empty(R, self.Hq * self.D, dtype=self.tdt, device=self.dev)
+        a = torch.empty(R, H, dtype=m.tdt, device=self.dev)
+        qkv = torch.empty(R, (m.Hq + 2 * m.Hkv) * m.D, device=self.dev)
+        q = torch.empty(R, m.Hq * m.D, dtype=m.tdt, device=self.dev)
+        att = torch.empty(R, m.Hq * m.D, dtype=m.tdt, device=self.dev)
         gu = torch.empty(R, 2 * I, device=self.dev)
-        act = torch.empty(R, I, dtype=self.tdt, device=self.dev)
-        for l, (w, ws) in enumerate(zip(self.pf_layers, self.layers)):
-            ops.rownorm(h, w["g1"], None, self.eps, rows=R, C_=H, rms=True, out_act=a, dtype=dt)
+        act = torch.empty(R, I, dtype=m.tdt, device=self.dev)
+        for l, (w, ws) in enumerate(zip(m.pf_layers, m.layers)):
+            ops.rownorm(h, w["g1"], None, m.eps, rows=R, C_=H, rms=True, out_act=a, dtype=dt)
             ops.linear(a, w["wqkv"], H, dtype=dt, bias=ws["bqkv"], out_f32=qkv)
-            ops.rope_kv_store(qkv, self.inv_freq, pos, q, self.kc[l], self.vc[l], block_table, B=B, rows=Lm,
-                              Hq=self.Hq, Hkv=self.Hkv, page=self.page, dtype=dt)
-            ops.paged_attn(q, pos, self.kc[l], self.vc[l], block_table, att, B=B, rows=Lm, Hq=self.Hq,
-                           Hkv=self.Hkv, page=self.page, dtype=dt)
-            ops.linear(att, w["wo"], self.Hq * self.D, dtype=dt, residual=h, out_f32=h)
-            ops.rownorm(h, w["g2"], None, self.eps, rows=R, C_=H, rms=True, out_act=a, dtype=dt)
+            ops.rope_kv_store(qkv, m.inv_freq, pos, q, m.kc[l], m.vc[l], block_table, B=B, rows=Lm,
+                              Hq=m.Hq, Hkv=m.Hkv, page=m.page, dtype=dt)
+            ops.paged_attn(q, pos, m.kc[l], m.vc[l], block_table, att, B=B, rows=Lm, Hq=m.Hq,
+                           Hkv=m.Hkv, page=m.page, dtype=dt)
+            ops.linear(att, w["wo"], m.Hq * m.D, dtype=dt, residual=h, out_f32=h)
+            ops.rownorm(h, w["g2"], None, m.eps, rows=R, C_=H, rms=True, out_act=a, dtype=dt)
             ops.linear(a, w["wgu"], H, dtype=dt, out_f32=gu)
             ops.swiglu(gu, act, rows=R, I=I, dtype=dt)
             ops.linear(act, w["wdown"], I, dtype=dt, residual=h, out_f32=h)
+
+    def _prefill(self, x, pos0, slot, head=False, norm_out=None):
+        """The one prompt entry: the rows x [n, H] go into `slot`'s cache at positions pos0.. in chunks of <= 64 through the
+        engine's prompt family (_prefill_chunk; a chunk's hidden rows live in staging buffers the next chunk overwrites, so
+        what a caller wants of them is taken here).
+        head: the last row's hidden state becomes the slot's h / h_act, what _tail projects (start, feed).
+        norm_out fp32 [n, H]: receives hidden_states[-1], the backbone's final RMSNorm of every row (forward_rows)."""
+        m = self.model
+        x = x.to(self.dev, torch.float32).contiguous()
+        for c0 in range(0, x.shape[0], 64):
+            hc, hca = self._prefill_chunk(x[c0:c0 + 64], pos0 + c0, slot)
+            if norm_out is not None:
+                ops.rownorm(hc, m.norm_w, None, m.eps, rows=hc.shape[0], C_=m.H, rms=True, out_f32=norm_out[c0:c0 + 64], dtype=F32)
+        if head:
+            self.h[slot].copy_(hc[-1])
+            self.h_act[slot].copy_(hca[-1])
 
     def _prefill_chunk(self, xc, pos0, b):
         """<= 64 prompt rows of sequence b through the layers at cache position pos0.  One hipGraph per chunk length over
         static staging buffers: a 50-row prompt is 144 launches, which the host issues in ~1.5 ms eagerly (32 prompts
         in front of a batch: ~50 ms with the GPU mostly idle) and the graph replays in ~0.4 ms."""
         rows = xc.shape[0]
-        if self.h2 or self.wplanes:
-            # the decode packs are fp16 / weight planes (csrc/decode.hip only): prompt rows go through the windowed GEMM
+        if self.prompt_on == "gemm":
             hc = xc.to(self.dev, torch.float32).clone()
             self._gemm_layers(hc, 1, rows, torch.tensor([pos0], dtype=torch.int32, device=self.dev), self.block_table[b:b + 1].contiguous())
             return hc, hc.to(self.tdt)
-        if not self.use_graphs:
-            hc = xc.clone()
-            hca = hc.to(self.tdt)
-            pos = torch.tensor([pos0], dtype=torch.int32, device=self.dev)
-            self._layers(hc, hca, 1, rows, pos, self.block_table[b:b + 1])
-            return hc, hca
         if not hasattr(self, "_pf"):
             self._pf = dict(h=torch.zeros(64, self.H, device=self.dev), ha=torch.zeros(64, self.H, dtype=self.tdt, device=self.dev),
                             pos=torch.zeros(1, dtype=torch.int32, device=self.dev),
@@ -581,7 +587,7 @@ class LlmEngine:
         pf["pos"].fill_(pos0)
         pf["bt"].copy_(self.block_table[b:b + 1])
         if rows not in pf["graphs"]:
-            pf["graphs"][rows] = Graphed(lambda r=rows: self._layers(pf["h"][:r], pf["ha"][:r], 1, r, pf["pos"], pf["bt"]), True)
+            pf["graphs"][rows] = Graphed(lambda r=rows: self._layers(pf["h"][:r], pf["ha"][:r], 1, r, pf["pos"], pf["bt"]), self.use_graphs)
         pf["graphs"][rows]()
         return pf["h"][:rows], pf["ha"][:rows]
 
@@ -606,15 +612,11 @@ class LlmEngine:
         n = x.shape[0]
         if pos0 + n > self.max_pages * self.page:
             raise RuntimeError("sequence exceeds the KV cache")
-        x = x.to(self.dev, torch.float32).contiguous()
         if pos0 == 0:
             self.release(0)
         self._set_pages(0, pos0 + n)
         out = torch.empty(n, self.H, device=self.dev)
-        for c0 in range(0, n, 64):
-            c1 = min(n, c0 + 64)
-            hc, _ = self._prefill_chunk(x[c0:c1], pos0 + c0, 0)
-            ops.rownorm(hc, self.norm_w, None, self.eps, rows=c1 - c0, C_=self.H, rms=True, out_f32=out[c0:c1], dtype=F32)
+        self._prefill(x, pos0, 0, norm_out=out)
         return out
 
     def compact_from(self, big: "LlmEngine", idx: List[int]):
@@ -631,17 +633,19 @@ class LlmEngine:
         self.out_tokens[:n].copy_(big.out_tokens[ii])
         self.sampled[:n].copy_(big.sampled[ii])
         self.x_in[:n].copy_(big.x_in[ii])
-        self.block_table.fill_(self.trash_page)           # idle slots append their (ignored) KV to the scratch page
+        self.block_table.fill_(self.model.trash_page)           # idle slots append their (ignored) KV to the scratch page
         self.block_table[:n].copy_(big.block_table[ii])
         self.seed, self.want_logp = big.seed, False
         self.mode, self.top_p, self.top_k, self.win_size, self.tau_r = big.mode, big.top_p, big.top_k, big.win_size, big.tau_r
         self.samp[:, :n] = big.samp[:, ii]                # every survivor keeps its own sampler and seed
         self._samp_host[:n] = [dict(big._samp_host[i]) for i in idx]
         self.forced = None
-        self._fresh_decode_graph((True, False))
+        self._fresh_decode_graph()
 
-    def _fresh_decode_graph(self, key):
-        if self._decode is None or getattr(self, "_graph_key", None) != key:
+    def _fresh_decode_graph(self):
+        # forced and logp_out are baked POINTER arguments of the sampler launch (seeds, sampler parameters: device data)
+        key = (self.forced is None, self.want_logp)
+        if self._decode is None or self._graph_key != key:
             if self._decode is not None:
                 self._decode.release()
             self._decode = Graphed(self._decode_step, self.use_graphs)
@@ -669,7 +673,7 @@ class LlmEngine:
         running every request alone under the same seed and sampler).  A request's sampler (dict, see start) and seed are
         optional; None / absent = the engine's sampler attributes and `seed`."""
         self.seed, self.want_logp, self.forced = int(seed), False, None
-        self._fresh_decode_graph((True, False))
+        self._fresh_decode_graph()
         st = torch.zeros(8, self.B, dtype=torch.int32)
         st[ST_FIN] = 1
         self.state.copy_(st)
@@ -712,22 +716,18 @@ class LlmEngine:
         self._write_samplers([self._sampler_fields(sampler, None)])
         self._st = dict(rows=0, calls=0, hist=0, seq=int(seq_id), last=None)
         self.sampled.fill_(-1)
-        self._fresh_decode_graph((True, self.want_logp))
+        self._fresh_decode_graph()
 
-    def embed_text(self, tok: torch.Tensor) -> torch.Tensor:
-        """llm.model.model.embed_tokens rows, fp32 [n, H]."""
+    def embed_text(self, tok: torch.Tensor, table=None) -> torch.Tensor:
+        """llm.model.model.embed_tokens rows (or `table`'s), fp32 [n, H]."""
         tok = tok.reshape(-1).to(self.dev, torch.int64)
         x = torch.empty(tok.numel(), self.H, device=self.dev)
         if tok.numel():
-            ops.gather_rows(tok, self.embed_tokens, out_f32=x, dtype=F32)
+            ops.gather_rows(tok, self.embed_tokens if table is None else table, out_f32=x, dtype=F32)
         return x
 
     def embed_speech(self, tok: torch.Tensor) -> torch.Tensor:
-        tok = tok.reshape(-1).to(self.dev, torch.int64)
-        x = torch.empty(tok.numel(), self.H, device=self.dev)
-        if tok.numel():
-            ops.gather_rows(tok, self.speech_emb, out_f32=x, dtype=F32)
-        return x
+        return self.embed_text(tok, self.speech_emb)
 
     def _upload_state(self, pos, ignore_eos):
         s = self._st
@@ -747,12 +747,7 @@ class LlmEngine:
             self._upload_state(s["rows"], ignore_eos)
             self._decode()
         else:
-            x = x.to(self.dev, torch.float32).contiguous()
-            for c0 in range(0, n, 64):
-                c1 = min(n, c0 + 64)
-                hc, hca = self._prefill_chunk(x[c0:c1], s["rows"] + c0, 0)
-            self.h[0].copy_(hc[-1])
-            self.h_act[0].copy_(hca[-1])
+            self._prefill(x, s["rows"], 0, head=True)
             self._upload_state(s["rows"] + n - 1, ignore_eos)
             self._tail(1)
         tok = int(self.sampled[0, s["calls"]].item())
@@ -779,6 +774,12 @@ class LlmEngine:
         if token < self.eos:
             s["last"] = token
         s["hist"] += 1
+
+    def accepted(self, slots=None, n=None) -> List[torch.Tensor]:
+        """The accepted ids of `slots` (default: every slot) as int64 device tensors; n: state[ST_NOUT] as a host list, for a
+        caller that has read it already."""
+        n = self.state[ST_NOUT].tolist() if n is None else n
+        return [self.out_tokens[s_, :n[s_]].to(torch.int64) for s_ in (range(self.B) if slots is None else slots)]
 
     def tokens(self) -> List[List[int]]:
         n = self.state[ST_NOUT].tolist()

@@ -15,7 +15,7 @@ from . import ops
 from ._lib import BF16, F32, TORCH_DT, X2, X3, is_split
 from .dac import DacDecoderEngine
 from .flow import FlowEngine, Graphed
-from .llm import LlmEngine
+from .llm import ST_FIN, ST_NOUT, ST_POS, LlmEngine
 
 TOKEN_RATE = 25          # FSQ tokens per second (config.yaml:12)
 SAMPLE_RATE = 24000
@@ -125,8 +125,7 @@ class TtsEngine:
             maxs.append(exact_steps[b] if exact_steps is not None else int(n * max_ratio))
         self.llm.start(xs, mins, maxs, seed=seed, samplers=samplers, seeds=seeds)
         self.llm.run(max(maxs))
-        n = self.llm.state[2].tolist()
-        return [self.llm.out_tokens[b, :n[b]].to(torch.int64) for b in range(B)]
+        return self.llm.accepted()
 
     @torch.no_grad()
     def token2wav(self, token: torch.Tensor, prompt_token: torch.Tensor, prompt_feat: torch.Tensor,
@@ -183,7 +182,6 @@ class TtsEngine:
         Yields waveform chunks [1, n] (device); `latents_out` (a list) receives the latent frames [n, 80] each chunk was
         rendered from; `forced` [1, steps] teacher-forces the accepted ids (LlmEngine.start).  cache=True: hops solve only
         their new frames (FlowEngine.StreamState); cache=False recomputes all frames at every hop, as the reference does."""
-        from .llm import ST_FIN, ST_NOUT
         assert self.llm.B == 1
         z = torch.zeros(1, 0, dtype=torch.long, device=self.dev)
         zf = torch.zeros(1, 0, 80, device=self.dev)
@@ -429,7 +427,6 @@ class TtsEngine:
         utterances still have to do after their last token is what the step ends on."""
         import queue as queue_mod
         import threading
-        from .llm import ST_FIN, ST_NOUT, ST_POS
         B = len(texts)
         NS = self.llm.B                                   # decode slots; more utterances than slots queue up and are admitted
         assert B >= NS and (overlap or B == NS)           # into slots as they free (continuous batching, LlmEngine.admit)
@@ -455,8 +452,7 @@ class TtsEngine:
             self.llm.start(xs, mins, maxs, seed=seed, samplers=samplers, seeds=seeds)
             self.llm.run(max(maxs), poll_every)
             n = self.llm.state[ST_NOUT].tolist()
-            for b in range(B):
-                toks[b] = self.llm.out_tokens[b, :n[b]].to(torch.int64)
+            toks[:] = self.llm.accepted(n=n)
             order = sorted(range(B), key=lambda b: (n[b], b))
             for grp in self._groups(order, [2 * (v + plen[b]) for b, v in enumerate(n)], group_size, max_pad_ratio, frame_quantum):
                 self._flow_dac_group(grp, toks, flow_embeddings, wavs, frame_quantum, prompts=prompts)
@@ -529,10 +525,10 @@ class TtsEngine:
             n = eng.state[ST_NOUT].tolist()
             new = sorted([s_ for s_ in range(len(slots)) if (fin[s_] or final) and slots[s_] not in seen],
                          key=lambda s_: (n[s_], slots[s_]))
-            for s_ in new:
+            for s_, ids in zip(new, eng.accepted(new, n)):
                 b = slots[s_]
                 seen.add(b)
-                toks[b] = eng.out_tokens[s_, :n[s_]].to(torch.int64)
+                toks[b] = ids
                 pending.append(b)
                 arrived[b] = steps_done[0]
             while waiting and not final:                            # a freed slot takes the next queued utterance

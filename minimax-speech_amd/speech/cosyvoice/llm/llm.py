@@ -349,6 +349,7 @@ class Qwen2LM(EngineHost):
             lm_input = None
 
     def _decode_loop(self, eng, x, min_len, max_len, sampling=25):
+        from mmx.llm import ST_FIN, ST_NOUT
         spec = self._sampler_spec()
         if spec is None:
             yield from self._decode_loop_host(eng, x, min_len, max_len, sampling)
@@ -358,11 +359,11 @@ class Qwen2LM(EngineHost):
         done = 1
         while True:
             st = eng.state[:, 0].tolist()
-            toks = eng.out_tokens[0, sent:st[2]].tolist()
+            toks = eng.out_tokens[0, sent:st[ST_NOUT]].tolist()
             for t in toks:
                 yield t
-            sent = st[2]
-            if st[3] or done >= max_len:
+            sent = st[ST_NOUT]
+            if st[ST_FIN] or done >= max_len:
                 break
             for _ in range(min(8, max_len - done)):
                 eng.step()

@@ -182,9 +182,7 @@ def test_batched_prefill_matches_per_sequence_prefill(dt, tol):
     z = torch.zeros(1, 0, dtype=torch.long, device="cuda")
     outs = []
     for batched in (True, False):
-        eng = LlmEngine(sd, dtype=dt, max_batch=B, max_ctx=256)
-        if not batched:
-            eng.pf_layers = []
+        eng = LlmEngine(sd, dtype=dt, max_batch=B, max_ctx=256, prompt_on=(None if batched else "skinny"))
         xs = [eng.build_lm_input(t, z, z) for t in texts]
         eng.start(xs, [20] * B, [20] * B, seed=5)
         logits = eng.logits.clone()

@@ -263,12 +263,8 @@ def test_lm_split_decode_v2_equals_round2_kernel(golden_dir):
         texts = [torch.randint(0, 151936, (1, 6 + b % 5), generator=g).cuda() for b in range(B)]
         lp = {}
         for v2 in (False, True):
-            LlmEngine.use_v2 = v2                      # (read at construction: the round-2 kernel takes the bf16 packs)
-            try:
-                eng = LlmEngine(sd, dtype=X3, max_batch=B, max_ctx=128, use_graphs=False, lm_planes="bf16x3")
-            finally:
-                LlmEngine.use_v2 = True
-            eng.use_v2 = v2
+            eng = LlmEngine(sd, dtype=X3, max_batch=B, max_ctx=128, use_graphs=False, lm_planes="bf16x3",
+                            decode_on=("planes" if v2 else "skinny"))
             xs = [eng.build_lm_input(t, z, z) for t in texts]
             eng.start(xs, [12] * B, [12] * B, seed=3, want_logp=True)
             for _ in range(6):

@@ -35,7 +35,7 @@ def main():
     a = ap.parse_args()
     dt = {"bf16": 1, "f32": 0, "x": 2}[a.dtype]
     from mmx.llm import LlmEngine
-    LlmEngine.use_v2 = not a.v1
+    LlmEngine.use_v2 = not a.v1                           # (read when the engines are built)
     LlmEngine.prefetch = a.prefetch
     if a.lm_planes:
         LlmEngine.lm_planes = a.lm_planes
