@@ -246,9 +246,14 @@ extern "C" int mmx_conv_cout1_tanh(const void* act, int64_t a_bs, int T_, int C,
     size_t esz = dtype == MMX_BF16 ? 2 : 4;
     size_t lds = (size_t)k * C * 4 + (size_t)(256 + k - 1) * C * esz;
     MMX_CHECK_ARG(lds <= 160 * 1024);
-    if (dtype == MMX_BF16) hipLaunchKernelGGL(conv_cout1_kernel<bf16_t>, grid, dim3(256), lds, stream, (const bf16_t*)act, a_bs, T_, C, k, w, bias, slope, use_tanh, out, o_bs);
-    else if (dtype == MMX_F32) hipLaunchKernelGGL(conv_cout1_kernel<float>, grid, dim3(256), lds, stream, (const float*)act, a_bs, T_, C, k, w, bias, slope, use_tanh, out, o_bs);
-    else return MMX_EARG;
+    // above 64 KB the launch needs the per-function opt-in, as the GEMM's larger tiles do (fp32 / split builds from C = 64 at k = 7)
+    if (dtype == MMX_BF16) {
+        MMX_LDS_OPT_IN(conv_cout1_kernel<bf16_t>, lds);
+        hipLaunchKernelGGL(conv_cout1_kernel<bf16_t>, grid, dim3(256), lds, stream, (const bf16_t*)act, a_bs, T_, C, k, w, bias, slope, use_tanh, out, o_bs);
+    } else if (dtype == MMX_F32) {
+        MMX_LDS_OPT_IN(conv_cout1_kernel<float>, lds);
+        hipLaunchKernelGGL(conv_cout1_kernel<float>, grid, dim3(256), lds, stream, (const float*)act, a_bs, T_, C, k, w, bias, slope, use_tanh, out, o_bs);
+    } else return MMX_EARG;
     MMX_LAUNCH_CHECK();
     return MMX_OK;
 }

@@ -173,10 +173,10 @@ def mask_rows(x, rowmask, *, rows, C_, dtype):
     check(load().mmx_mask_rows(_p(x), i64(rows), C_, _p(rowmask), dtype, stream()), "mmx_mask_rows")
 
 
-def gather_rows(ids, table, *, scale=1.0, rowmask=None, out_f32=None, out_act=None, dtype=F32):
+def gather_rows(ids, table, *, scale=1.0, rowmask=None, out_f32=None, out_act=None, dtype=F32, ldo_f=None, ldo_a=None):
     n, C_ = ids.numel(), table.shape[1]
-    check(load().mmx_gather_rows(_p(ids), n, _p(table), C_, C.c_float(scale), _p(rowmask), _p(out_f32), i64(C_),
-                                 _p(out_act), i64(C_), dtype, stream()), "mmx_gather_rows")
+    check(load().mmx_gather_rows(_p(ids), n, _p(table), C_, C.c_float(scale), _p(rowmask), _p(out_f32), i64(ldo_f or C_),
+                                 _p(out_act), i64(ldo_a or C_), dtype, stream()), "mmx_gather_rows")
 
 
 def copy2d(src, src_dt, ibs, irs, ics, dst, dst_dt, obs, ors, ocs, rows, cols, batch=1, rep=1):
@@ -491,8 +491,8 @@ def decode_attn(qkv, inv_freq, pos, kc, vc, block_table, out, *, B, Hq, Hkv, pag
                                  i64(Hq * 64), dtype, int(bool(out_packed)) | (2 if per_head else 0) | (8 if out_split == "f16" else (4 if out_split else 0)) | (16 if one_head else 0), stream()), "mmx_decode_attn")
 
 
-def swiglu(gu, out, *, rows, I, dtype):
-    check(load().mmx_swiglu(_p(gu), i64(2 * I), rows, I, _p(out), i64(I), dtype, stream()), "mmx_swiglu")
+def swiglu(gu, out, *, rows, I, dtype, ldgu=None, ldo=None):
+    check(load().mmx_swiglu(_p(gu), i64(ldgu or 2 * I), rows, I, _p(out), i64(ldo or I), dtype, stream()), "mmx_swiglu")
 
 
 def sample_step(logits, state, out_tokens, speech_emb, next_x, *, V, B, eos_id, seed, top_k=25, top_p=0.8,
