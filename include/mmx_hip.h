@@ -233,6 +233,11 @@ int mmx_vae_sample(const float* ml, const float* noise, int64_t rows, int D, flo
 /* x[row][:] = 0 where rowmask[row] == 0, in place; x is T [rows][C] (C a multiple of 16 bytes).  The rows beyond a member's length
  * of a zero-padded batch behind a ConvTranspose1d (dac-vae/model.py:252-284), whose GEMM rows straddle that boundary. */
 int mmx_mask_rows(void* x, int64_t rows, int C, const float* rowmask, int dtype, hipStream_t stream);
+/* Masked mean over the rows of a time-major fp32 tensor (speech/cosyvoice/llm/llm.py:80-88, LearnableSpeakerEncoder's mean pooling):
+ *   out[b][c] = sum_t x[b][t][c] * mask[b][t] / max(sum_t mask[b][t], 1);  mask fp32 [B][m_bs >= rows] or NULL (plain mean).
+ * x [B][rows][C] with batch stride x_bs; out T [B][ldo].  Summation order is fixed (no atomics). */
+int mmx_pool_rows(const float* x, int64_t x_bs, int rows, int C, int batch, const float* mask, int64_t m_bs, void* out,
+                  int64_t ldo, int dtype, hipStream_t stream);
 /* Cache prefetch: reads the byte ranges [p_i, p_i + n_i) (16-byte aligned, n_i multiples of 16; NULL = none) with default-policy
  * loads and keeps nothing, so the lines are left in L2 / the Infinity Cache for a later launch (the next LM layer's weights while
  * the current layer computes: a side stream of the captured decode step).  sink: 4 writable bytes (never written in practice). */
@@ -474,6 +479,31 @@ typedef struct {
     float slope;
 } MmxDacRuParams;
 int mmx_dac_ru(const MmxDacRuParams* p, int dtype, int bm, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Reference audio -> log-mel frames in one launch (speech/matcha/utils/audio.py:45-82 with center=False: reflect padding by
+ * pad = (n_fft - hop) / 2, torch.stft with a periodic Hann window of win_size == n_fft, sqrt(re^2 + im^2 + 1e-9), the mel
+ * filterbank, log(max(v, 1e-5))); with `gain` also the peak normalisation of cosyvoice/dataset/processor.py:385-387.
+ *   wave  fp32 [B][w_bs >= L] mono rows; gain fp32 [B] or NULL: sample * gain[b] (rounded to fp32) is what is analysed;
+ *   lens  int32 [B] or NULL: valid samples per member of a zero-padded batch, each reflected at its OWN end; h_lens: the same
+ *         values in HOST memory (given exactly when lens is), so that the call can refuse a member before anything is launched.
+ *   Member b has frames(len) = (len + 2 * pad - n_fft) / hop + 1 frames (len / hop when hop divides len); frame t covers the
+ *   padded samples t * hop .. t * hop + n_fft - 1.  The reflection is index arithmetic on the row: no padded copy exists.
+ *   basis bf16 [3][2 * nbp][n_fft], nbp = n_bins rounded up to 32: three planes hi + mid + lo of the float64 values
+ *         hann[k] * cos(2 pi (bin0 + i) k / n_fft) (row 32 * (i / 16) + i % 16) and hann[k] * sin(..) (that row + 16), rows of bins
+ *         >= n_bins zero, each plane in mmx_pack_skinny order;
+ *   filt  bf16 [3][mp][nbp], mp = n_mels rounded up to 16: three planes of the fp32 filterbank columns bin0 .. bin0 + n_bins - 1
+ *         (zero padded), each plane in mmx_pack_skinny order.  Only bins with a non-zero filter weight need to be passed
+ *         (fmax = 8000 at 24 kHz, n_fft 1920: bins 1 .. 639 of 961).
+ *   Both products run on the bf16 MFMA with the samples / magnitudes split into three bf16 terms in the kernel and every term
+ *   pair s + p < 3 kept, fp32 accumulation: one arithmetic for every `dtype`, which only selects the type T of out_tm.
+ *   out_cm fp32 [B][n_mels][ldo >= T] (the reference function's layout) and / or out_tm T [B][T][n_mels] (time-major, the speaker
+ *   encoder's input); frames t >= frames(lens[b]) are written as 0 (the collate's zero padding, processor.py:658).
+ * MMX_EARG: n_fft % 32 != 0, n_mels > 128, hop % 8 != 0, n_fft - hop odd, a member (or L) with at most pad samples (the reflection
+ *   is undefined; torch raises there too) or too few for one frame, T smaller than a member's frame count, or tables that do not fit 160 KB of LDS. */
+int mmx_logmel(const float* wave, int64_t w_bs, int L, int B, const float* gain, const int32_t* lens, const int32_t* h_lens,
+               const void* basis, const void* filt, int n_fft, int hop, int bin0, int n_bins, int n_mels, float* out_cm,
+               int64_t ldo, void* out_tm, int T, int dtype, hipStream_t stream);
 
 #ifdef __cplusplus
 }

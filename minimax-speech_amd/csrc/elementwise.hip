@@ -357,6 +357,43 @@ extern "C" int mmx_mask_rows(void* x, int64_t rows, int C, const float* rowmask,
     return MMX_OK;
 }
 
+// ---------------------------------------------------------------------------- masked mean over rows
+// out[b][c] = sum_t x[b][t][c] * mask[b][t] / max(sum_t mask[b][t], 1)   (mask NULL: the plain mean over T rows):
+// LearnableSpeakerEncoder's mean pooling (speech/cosyvoice/llm/llm.py:80-88).  A workgroup takes 64 channels of one batch member:
+// 4 row groups x 64 channels, each thread sums rows rg, rg + 4, ... in order, the four partial sums are added in group order
+// (deterministic: no atomics).
+template <typename T>
+__global__ __launch_bounds__(256) void pool_rows_kernel(const float* __restrict__ x, long x_bs, int rows, int C,
+                                                        const float* __restrict__ mask, long m_bs, T* __restrict__ out, long ldo) {
+    __shared__ float part[4][64], cnt[4];
+    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, c = blockIdx.x * 64 + cl, b = blockIdx.y;
+    float s = 0.f, n = 0.f;
+    for (int t = rg; t < rows; t += 4) {
+        const float m = mask ? mask[(long)b * m_bs + t] : 1.f;
+        n += m;
+        if (c < C) s += x[(long)b * x_bs + (long)t * C + c] * m;
+    }
+    part[rg][cl] = s;
+    if (cl == 0) cnt[rg] = n;
+    __syncthreads();
+    if (rg == 0 && c < C) {
+        const float tot = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl];
+        const float den = fmaxf(((cnt[0] + cnt[1]) + cnt[2]) + cnt[3], 1.f);
+        out[(long)b * ldo + c] = Cvt<T>::from_f(tot / den);
+    }
+}
+extern "C" int mmx_pool_rows(const float* x, int64_t x_bs, int rows, int C, int batch, const float* mask, int64_t m_bs, void* out,
+                             int64_t ldo, int dtype, hipStream_t stream) {
+    dtype = MMX_ACT_DTYPE(dtype);
+    MMX_CHECK_ARG(x && out && rows > 0 && C > 0 && batch > 0 && batch <= 65535 && ldo >= C && x_bs >= (int64_t)rows * C);
+    MMX_CHECK_ARG(!mask || m_bs >= rows);
+    const dim3 grid((C + 63) / 64, batch);
+    if (dtype == MMX_BF16) hipLaunchKernelGGL(pool_rows_kernel<bf16_t>, grid, dim3(256), 0, stream, x, (long)x_bs, rows, C, mask, (long)m_bs, (bf16_t*)out, (long)ldo);
+    else hipLaunchKernelGGL(pool_rows_kernel<float>, grid, dim3(256), 0, stream, x, (long)x_bs, rows, C, mask, (long)m_bs, (float*)out, (long)ldo);
+    MMX_LAUNCH_CHECK();
+    return MMX_OK;
+}
+
 // ---------------------------------------------------------------------------- weight prefetch into L2 / Infinity Cache
 // Reads up to four byte ranges with default-policy 16-byte loads and keeps nothing: the lines stay in the issuing XCD's L2 and in
 // the memory-side Infinity Cache.  Launched on a SIDE stream of the captured LM decode step with the NEXT layer's packed weights

@@ -173,6 +173,11 @@ def mask_rows(x, rowmask, *, rows, C_, dtype):
     check(load().mmx_mask_rows(_p(x), i64(rows), C_, _p(rowmask), dtype, stream()), "mmx_mask_rows")
 
 
+def pool_rows(x, out, *, B, T, C_, dtype, mask=None):
+    """out[b][:] = masked mean over the T rows of x [B][T][C] fp32 (mmx_pool_rows; mask fp32 [B][T] or None = plain mean)."""
+    check(load().mmx_pool_rows(_p(x), i64(T * C_), T, C_, B, _p(mask), i64(T), _p(out), i64(C_), dtype, stream()), "mmx_pool_rows")
+
+
 def gather_rows(ids, table, *, scale=1.0, rowmask=None, out_f32=None, out_act=None, dtype=F32, ldo_f=None, ldo_a=None):
     n, C_ = ids.numel(), table.shape[1]
     check(load().mmx_gather_rows(_p(ids), n, _p(table), C_, C.c_float(scale), _p(rowmask), _p(out_f32), i64(ldo_f or C_),

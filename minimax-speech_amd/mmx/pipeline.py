@@ -138,9 +138,34 @@ class TtsEngine:
         return self.dac.decode_time_major(zt, 1, T2)
 
     @torch.no_grad()
-    def tts(self, text, flow_embedding, prompt_text=None, llm_prompt_speech_token=None, flow_prompt_speech_token=None,
-            prompt_speech_feat=None, seed=0, exact_steps=None) -> torch.Tensor:
-        """One utterance, non-streaming (cli/model.py:321-386 `stream=False` branch)."""
+    def reference_embedding(self, reference_audio, sample_rate=24000, cache=None) -> torch.Tensor:
+        """A reference recording (a mono clip [n] / [1, n] on the device at `sample_rate`, or a list of clips of one speaker)
+        -> the speaker embedding [1, 192] the flow is conditioned on: crop + peak gain, mmx_logmel, the learnable speaker
+        encoder (SpeakerEncoderEngine.embed_audio).  Needs a flow checkpoint with `speaker_encoder.*` (use_speaker_encoder: True).
+        cache (a dict): one embedding per distinct clip object."""
+        if self.flow.spk_enc is None:
+            raise RuntimeError("reference_audio needs the learnable speaker encoder: the flow state dict has no speaker_encoder.* "
+                               "weights (speech/config.yaml use_speaker_encoder: True)")
+        key = id(reference_audio)
+        if cache is not None and key in cache:
+            return cache[key][1]
+        clips = list(reference_audio) if isinstance(reference_audio, (list, tuple)) else [reference_audio]
+        e = self.flow.spk_enc.embed_audio(clips, sample_rate)
+        if cache is not None:
+            cache[key] = (reference_audio, e)              # the clip is kept alive with its id
+        return e
+
+    def _embedding_arg(self, flow_embedding, reference_audio, sample_rate):
+        if (flow_embedding is None) == (reference_audio is None):
+            raise ValueError("give exactly one of flow_embedding and reference_audio")
+        return flow_embedding if reference_audio is None else self.reference_embedding(reference_audio, sample_rate)
+
+    @torch.no_grad()
+    def tts(self, text, flow_embedding=None, prompt_text=None, llm_prompt_speech_token=None, flow_prompt_speech_token=None,
+            prompt_speech_feat=None, seed=0, exact_steps=None, reference_audio=None, sample_rate=24000) -> torch.Tensor:
+        """One utterance, non-streaming (cli/model.py:321-386 `stream=False` branch).  reference_audio (instead of
+        flow_embedding): the voice as a recording, see reference_embedding."""
+        flow_embedding = self._embedding_arg(flow_embedding, reference_audio, sample_rate)
         z = torch.zeros(1, 0, dtype=torch.long, device=self.dev)
         toks = self.generate_tokens([text], [prompt_text if prompt_text is not None else z],
                                     [llm_prompt_speech_token if llm_prompt_speech_token is not None else z],
@@ -161,9 +186,9 @@ class TtsEngine:
         return torch.cat([w[:n] / s_, w[n:] / s_]).to(device)
 
     @torch.no_grad()
-    def tts_stream(self, text, flow_embedding, seed=0, exact_steps=None, token_hop=25, latents_out=None, forced=None,
+    def tts_stream(self, text, flow_embedding=None, seed=0, exact_steps=None, token_hop=25, latents_out=None, forced=None,
                    cache=True, prompt_text=None, llm_prompt_speech_token=None, flow_prompt_speech_token=None,
-                   prompt_speech_feat=None):
+                   prompt_speech_feat=None, reference_audio=None, sample_rate=24000):
         """Streaming synthesis of one (long) utterance: BASELINE config 5 / cli/model.py:336-378 (`stream=True`), zero-shot
         prompts included (prompt_text / llm_prompt_speech_token condition the LM, llm.py:691-703; flow_prompt_speech_token /
         prompt_speech_feat the flow, flow.py:472-498).
@@ -181,8 +206,11 @@ class TtsEngine:
         renderings (utils/common.py:142-150 fade_in_out, window of model.py:262 normalised to unit sum).
         Yields waveform chunks [1, n] (device); `latents_out` (a list) receives the latent frames [n, 80] each chunk was
         rendered from; `forced` [1, steps] teacher-forces the accepted ids (LlmEngine.start).  cache=True: hops solve only
-        their new frames (FlowEngine.StreamState); cache=False recomputes all frames at every hop, as the reference does."""
+        their new frames (FlowEngine.StreamState); cache=False recomputes all frames at every hop, as the reference does.
+        reference_audio (instead of flow_embedding): the voice as a recording (reference_embedding), embedded once before the
+        first hop."""
         assert self.llm.B == 1
+        flow_embedding = self._embedding_arg(flow_embedding, reference_audio, sample_rate)
         z = torch.zeros(1, 0, dtype=torch.long, device=self.dev)
         zf = torch.zeros(1, 0, 80, device=self.dev)
         pt = prompt_text if prompt_text is not None else z
@@ -397,10 +425,10 @@ class TtsEngine:
                   f"cfm {c:.1f} ms, dac {d:.1f} ms", flush=True)
 
     @torch.no_grad()
-    def tts_batch(self, texts, flow_embeddings, seed=0, exact_steps=None, group_size=8, max_pad_ratio=2.0,
+    def tts_batch(self, texts, flow_embeddings=None, seed=0, exact_steps=None, group_size=8, max_pad_ratio=2.0,
                   frame_quantum=32, overlap=True, poll_every=8, flow_workers=2, hold_steps=60, tail_active=0, polite=True,
                   prompt_texts=None, llm_prompt_speech_tokens=None, flow_prompt_speech_tokens=None,
-                  prompt_speech_feats=None, samplers=None, seeds=None) -> List[torch.Tensor]:
+                  prompt_speech_feats=None, samplers=None, seeds=None, reference_audio=None, sample_rate=24000) -> List[torch.Tensor]:
         """Throughput path for a batch of independent utterances (BASELINE config 4, one rank's share): one batched
         AR decode for all of them; as sequences finish (shortest first) their flow + DAC work — per-utterance
         conformer encoder, ODE solves batched over groups of similar length (zero padded + masked), DAC decode — is
@@ -420,6 +448,8 @@ class TtsEngine:
         then its (partial) group is issued, so the flow work of the long utterances is not left for after the last
         token (the rule counts decode steps, not wall time: the schedule, and with it the set of captured plans, is
         the same from run to run).
+        reference_audio: per utterance, a recording of the voice (reference_embedding) used where flow_embeddings[b] would be
+        (an entry of None keeps flow_embeddings[b]); every distinct clip object is embedded once, before the decode loop starts.
         polite: flow groups issued while the decode loop runs use FlowEngine.polite tiling (64-row tiles: fewer workgroups,
         more of the chip left to the decode loop's launches); the groups of the final harvest use the fastest tiling.
         tail_active > 0: once at most that many sequences are still decoding, a finished utterance no longer waits for
@@ -428,6 +458,15 @@ class TtsEngine:
         import queue as queue_mod
         import threading
         B = len(texts)
+        if reference_audio is None and flow_embeddings is None:
+            raise ValueError("give flow_embeddings or reference_audio")
+        if reference_audio is not None:
+            assert len(reference_audio) == B
+            seen = {}
+            if flow_embeddings is None:
+                flow_embeddings = [None] * B
+            flow_embeddings = [self._embedding_arg(flow_embeddings[b], None, sample_rate) if reference_audio[b] is None else
+                               self.reference_embedding(reference_audio[b], sample_rate, seen) for b in range(B)]
         NS = self.llm.B                                   # decode slots; more utterances than slots queue up and are admitted
         assert B >= NS and (overlap or B == NS)           # into slots as they free (continuous batching, LlmEngine.admit)
         assert (samplers is None or len(samplers) == B) and (seeds is None or len(seeds) == B)

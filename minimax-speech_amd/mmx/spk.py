@@ -12,8 +12,10 @@ from ._lib import BF16, F32, TORCH_DT
 
 
 class SpeakerEncoderEngine:
-    def __init__(self, sd: Dict[str, torch.Tensor], dtype=BF16, device="cuda", prefix="speaker_encoder", heads=8, pack_dtype=None):
+    def __init__(self, sd: Dict[str, torch.Tensor], dtype=BF16, device="cuda", prefix="speaker_encoder", heads=8, pack_dtype=None,
+                 mean_pooling=False):
         self.dtype, self.tdt, self.dev, self.heads = dtype, TORCH_DT[dtype], torch.device(device), heads
+        self.mean_pooling = mean_pooling
         dtype = dtype if pack_dtype is None else pack_dtype     # the code the weights are packed for (X2W: weight planes)
         f = lambda k: sd[k].detach().to(self.dev, torch.float32).contiguous()
         self.w_init, self.b_init = ops.pack_conv1d(f(prefix + ".init.weight"), dtype), f(prefix + ".init.bias")
@@ -33,13 +35,21 @@ class SpeakerEncoderEngine:
         self.gamma_l2 = torch.full((self.out_dim,), 1.0 / math.sqrt(self.out_dim), device=self.dev)
 
     @torch.no_grad()
-    def encode(self, mel: torch.Tensor) -> torch.Tensor:
-        """mel [B, 80, T] fp32 -> [B, 192] fp32, L2-normalised (LearnableSpeakerEncoder.forward, first-frame pooling)."""
-        dt, C, H = self.dtype, self.C, self.heads
+    def encode(self, mel: torch.Tensor, mask=None) -> torch.Tensor:
+        """mel [B, 80, T] fp32 -> [B, 192] fp32, L2-normalised (LearnableSpeakerEncoder.forward).  Pooling: frame 0, or with
+        mean_pooling the mean over frames, masked by `mask` [B, 1, T] when given (llm.py:80-88; the attention itself stays
+        unmasked, as in the reference)."""
         B, M, T = mel.shape
         mel = mel.to(self.dev, torch.float32).contiguous()
         mt = torch.empty(B, T, M, dtype=self.tdt, device=self.dev)
-        ops.copy2d(mel, F32, M * T, 1, T, mt, dt, T * M, M, 1, rows=T, cols=M, batch=B)
+        ops.copy2d(mel, F32, M * T, 1, T, mt, self.dtype, T * M, M, 1, rows=T, cols=M, batch=B)
+        return self.encode_time_major(mt, mask)
+
+    @torch.no_grad()
+    def encode_time_major(self, mt: torch.Tensor, mask=None) -> torch.Tensor:
+        """encode() on the encoder's own input layout: mt [B, T, 80] in the activation type (what mmx_logmel writes)."""
+        dt, C, H = self.dtype, self.C, self.heads
+        B, T, M = mt.shape
         x = torch.empty(B, T, C, device=self.dev)
         ops.conv1d(mt, self.w_init, T=T, Cin=M, k=1, dtype=dt, batch=B, bias=self.b_init, out_f32=x)
         hn = torch.empty(B, T, C, dtype=self.tdt, device=self.dev)
@@ -55,14 +65,50 @@ class SpeakerEncoderEngine:
             x2 = torch.empty(B, T, C, device=self.dev)
             ops.conv1d(att, w["wo"], T=T, Cin=C, k=1, dtype=dt, batch=B, bias=w["bo"], residual=x, out_f32=x2)
             x = x2
-        # frame 0 of every batch item -> Linear -> L2 normalise
+        # frame 0 (or the masked mean over frames) of every batch item -> Linear -> L2 normalise
         first = torch.empty(B, C, dtype=self.tdt, device=self.dev)
-        ops.copy2d(x, F32, T * C, C, 1, first, dt, C, C, 1, rows=1, cols=C, batch=B)
+        if self.mean_pooling:
+            if mask is not None:
+                mask = mask.to(self.dev, torch.float32).reshape(B, T).contiguous()
+            ops.pool_rows(x, first, B=B, T=T, C_=C, dtype=dt, mask=mask)
+        else:
+            ops.copy2d(x, F32, T * C, C, 1, first, dt, C, C, 1, rows=1, cols=C, batch=B)
         y = torch.empty(B, self.out_dim, device=self.dev)
         ops.linear(first, self.w_out, C, dtype=dt, bias=self.b_out, out_f32=y)
         out = torch.empty(B, self.out_dim, device=self.dev)
         ops.rownorm(y, self.gamma_l2, None, 1e-30, rows=B, C_=self.out_dim, rms=True, out_f32=out, dtype=F32)
         return out
+
+    def _normalise(self, e):
+        out = torch.empty_like(e)
+        ops.rownorm(e, self.gamma_l2, None, 1e-30, rows=e.shape[0], C_=self.out_dim, rms=True, out_f32=out, dtype=F32)
+        return out
+
+    @torch.no_grad()
+    def embed_audio(self, waves, sample_rate=24000, mel=None) -> torch.Tensor:
+        """One or more reference clips of ONE speaker (each [n] or [1, n] on the device) -> [1, 192]: the crop and peak gain of
+        processor.py:339-392 (mel.prepare_reference), one mmx_logmel launch over the zero-padded batch written time-major
+        straight into the encoder's input, then reference_embedding's mean over the clips and L2 normalisation.  With
+        mean_pooling the padded frames of the shorter clips are masked out of the pooling (reference_mel_masks).
+        mel: the LogMel setting (default: speech/config.yaml:183-191)."""
+        from . import mel as MEL
+        lm = mel if mel is not None else MEL.LogMel(device=self.dev)
+        assert lm.n_mels == self.mel_dim
+        segs, gains = zip(*(MEL.prepare_reference(w.to(self.dev), sample_rate) for w in waves))
+        lens = [s.shape[1] for s in segs]
+        if len(segs) == 1:
+            batch = segs[0]
+        else:
+            batch = torch.zeros(len(segs), max(lens), device=self.dev)
+            for i, s in enumerate(segs):
+                batch[i, :lens[i]] = s[0]
+        mt = lm(batch, lens=lens if len(segs) > 1 else None, gain=torch.cat(gains), time_major=True, dtype=self.dtype)
+        mask = None
+        if self.mean_pooling and len(segs) > 1:
+            frames = torch.tensor([lm.frames(n) for n in lens], device=self.dev)
+            mask = (torch.arange(mt.shape[1], device=self.dev)[None, :] < frames[:, None]).float()
+        e = self.encode_time_major(mt, mask)
+        return self._normalise(e.mean(dim=0, keepdim=True).contiguous())
 
     @torch.no_grad()
     def reference_embedding(self, reference_mels: torch.Tensor) -> torch.Tensor:
@@ -72,6 +118,4 @@ class SpeakerEncoderEngine:
             e = self.encode(reference_mels.reshape(B * N, M, T)).reshape(B, N, -1).mean(dim=1).contiguous()
         else:
             e = self.encode(reference_mels)
-        out = torch.empty_like(e)
-        ops.rownorm(e, self.gamma_l2, None, 1e-30, rows=e.shape[0], C_=self.out_dim, rms=True, out_f32=out, dtype=F32)
-        return out
+        return self._normalise(e)

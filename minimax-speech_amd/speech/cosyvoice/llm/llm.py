@@ -41,8 +41,8 @@ class LearnableSpeakerEncoder(EngineHost):
     def __init__(self, mel_dim: int = 80, model_dim: int = 512, output_dim: int = 192, num_blocks: int = 6,
                  num_heads: int = 8, dropout: float = 0.0, mean_pooling: bool = False):
         super().__init__()
-        if mean_pooling or model_dim // num_heads != 64:
-            raise NotImplementedError("first-frame pooling and 64-d heads (the reference's instantiation) only")
+        if model_dim // num_heads != 64:
+            raise NotImplementedError("64-d heads (the reference's instantiation) only")
         self.dim, self.mean_pooling, self.num_heads = model_dim, mean_pooling, num_heads
         register(self, shapes.speaker_encoder_manifest("speaker_encoder", mel_dim, model_dim, output_dim, num_blocks),
                  prefix="speaker_encoder.")
@@ -52,12 +52,14 @@ class LearnableSpeakerEncoder(EngineHost):
         dev = self._device()
         if self._engine is None:
             sd = {"speaker_encoder." + k: v for k, v in self.state_dict().items()}
-            self._engine = SpeakerEncoderEngine(sd, dtype=self.compute_dtype, device=dev, heads=self.num_heads)
+            self._engine = SpeakerEncoderEngine(sd, dtype=self.compute_dtype, device=dev, heads=self.num_heads,
+                                                mean_pooling=self.mean_pooling)
         return self._engine
 
     @torch.inference_mode()
     def forward(self, x, mask=None):
-        return self._eng().encode(x)
+        """llm.py:65-96: `mask` [B, 1, T] is read by the mean pooling alone (llm.py:80-88)."""
+        return self._eng().encode(x, mask)
 
 
 class Qwen2Encoder(nn.Module):

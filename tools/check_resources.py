@@ -27,7 +27,7 @@ GATED = [
     "est_resnet_kernel<unsigned short, 32, 4, 8, 2, false>", "est_resnet_kernel<unsigned short, 32, 4, 8, 2, true>",   # split build, 8 waves (cin = 256)
     "est_resnet_kernel<unsigned short, 32, 2, 4, 2, true>", "est_resnet_kernel<unsigned short, 32, 4, 4, 2, true>",
     "skinny3_kernel", "decode_attn_kernel", "sample_step_kernel", "attn_flash_kernel", "attn_flash_x_kernel", "attn_relpos",
-    "dac_ru_kernel", "gemm_win_kernel",
+    "dac_ru_kernel", "gemm_win_kernel", "logmel_kernel", "pool_rows_kernel",
 ]
 
 
