@@ -522,6 +522,9 @@ extern "C" int mmx_paged_attn(const void* q, int64_t ldq, int64_t q_bs, int B, i
     size_t lds = (64 + 8 + 4 * 64 + max_ctx) * 4;
     MMX_CHECK_ARG(lds <= 160 * 1024);
     dim3 grid(Hq, rows, B);
+    // the score row is sized by the block table (max_pages * page), not by the context: above 16056 positions it needs the opt-in
+    if (dtype == MMX_BF16) MMX_LDS_OPT_IN(paged_attn_kernel<bf16_t>, lds);
+    else if (dtype == MMX_F32) MMX_LDS_OPT_IN(paged_attn_kernel<float>, lds);
     if (dtype == MMX_BF16) hipLaunchKernelGGL(paged_attn_kernel<bf16_t>, grid, dim3(256), lds, stream, (const bf16_t*)q, ldq, q_bs, Hq, Hkv, scale, pos, (const bf16_t*)kc, (const bf16_t*)vc, block_table, max_pages, page, (bf16_t*)out, ldo, o_bs);
     else if (dtype == MMX_F32) hipLaunchKernelGGL(paged_attn_kernel<float>, grid, dim3(256), lds, stream, (const float*)q, ldq, q_bs, Hq, Hkv, scale, pos, (const float*)kc, (const float*)vc, block_table, max_pages, page, (float*)out, ldo, o_bs);
     else return MMX_EARG;

@@ -472,28 +472,35 @@ def skinny2(xs, wp, *, B, K, N, dtype, bias=None, ssq_in=None, eps=1e-6, epi=0, 
                              _p(part), i64(part.numel() if part is not None else 0), _p(tickets), dtype, stream()), "mmx_skinny2")
 
 
-def rope_kv_store(qkv, inv_freq, pos, q_out, kc, vc, block_table, *, B, rows, Hq, Hkv, page, dtype):
-    ld = (Hq + 2 * Hkv) * 64
-    check(load().mmx_rope_kv_store(_p(qkv), i64(ld), i64(rows * ld), B, rows, Hq, Hkv, 64, _p(inv_freq), _p(pos),
-                                   _p(q_out), i64(Hq * 64), i64(rows * Hq * 64), _p(kc), _p(vc), _p(block_table),
-                                   block_table.shape[1], page, dtype, stream()), "mmx_rope_kv_store")
+def rope_kv_store(qkv, inv_freq, pos, q_out, kc, vc, block_table, *, B, rows, Hq, Hkv, page, dtype, ldqkv=None, qkv_bs=None,
+                  ldq=None, q_bs=None):
+    """ldqkv / ldq: row pitches of qkv / q_out in elements (default: dense), qkv_bs / q_bs: their batch strides (default: rows * pitch)."""
+    ldqkv = (Hq + 2 * Hkv) * 64 if ldqkv is None else ldqkv
+    ldq = Hq * 64 if ldq is None else ldq
+    check(load().mmx_rope_kv_store(_p(qkv), i64(ldqkv), i64(rows * ldqkv if qkv_bs is None else qkv_bs), B, rows, Hq, Hkv, 64,
+                                   _p(inv_freq), _p(pos), _p(q_out), i64(ldq), i64(rows * ldq if q_bs is None else q_bs), _p(kc), _p(vc),
+                                   _p(block_table), block_table.shape[1], page, dtype, stream()), "mmx_rope_kv_store")
 
 
-def paged_attn(q, pos, kc, vc, block_table, out, *, B, rows, Hq, Hkv, page, dtype):
-    check(load().mmx_paged_attn(_p(q), i64(Hq * 64), i64(rows * Hq * 64), B, rows, Hq, Hkv, 64, C.c_float(0.125),
+def paged_attn(q, pos, kc, vc, block_table, out, *, B, rows, Hq, Hkv, page, dtype, ldq=None, q_bs=None, ldo=None, o_bs=None):
+    """ldq / ldo: row pitches of q / out in elements (default: dense), q_bs / o_bs: their batch strides (default: rows * pitch)."""
+    ldq = Hq * 64 if ldq is None else ldq
+    ldo = Hq * 64 if ldo is None else ldo
+    check(load().mmx_paged_attn(_p(q), i64(ldq), i64(rows * ldq if q_bs is None else q_bs), B, rows, Hq, Hkv, 64, C.c_float(0.125),
                                 _p(pos), _p(kc), _p(vc), _p(block_table), block_table.shape[1], page, _p(out),
-                                i64(Hq * 64), i64(rows * Hq * 64), dtype, stream()), "mmx_paged_attn")
+                                i64(ldo), i64(rows * ldo if o_bs is None else o_bs), dtype, stream()), "mmx_paged_attn")
 
 
 def decode_attn(qkv, inv_freq, pos, kc, vc, block_table, out, *, B, Hq, Hkv, page, dtype, rope_tab=None, out_packed=False,
-                per_head=False, out_split=False, one_head=False):
+                per_head=False, out_split=False, one_head=False, ldqkv=None, ldo=None):
     """per_head: the per-query-head kernel even where the GQA-shared one applies (measurements, tests); one_head: that kernel with
     one head per workgroup instead of two (the round-3 form; identical results).
     out_split: `out` receives split planes (the split build's decode step, include/mmx_hip.h): True = three bf16 planes,
-    "f16" = two fp16 planes (MMX_H2)."""
-    check(load().mmx_decode_attn(_p(qkv), i64((Hq + 2 * Hkv) * 64), B, Hq, Hkv, 64, _p(inv_freq), _p(rope_tab), _p(pos), _p(kc),
-                                 _p(vc), _p(block_table), block_table.shape[1], page, C.c_float(0.125), _p(out),
-                                 i64(Hq * 64), dtype, int(bool(out_packed)) | (2 if per_head else 0) | (8 if out_split == "f16" else (4 if out_split else 0)) | (16 if one_head else 0), stream()), "mmx_decode_attn")
+    "f16" = two fp16 planes (MMX_H2).
+    ldqkv / ldo: row pitches of qkv / a row-major `out` in elements (default: dense)."""
+    check(load().mmx_decode_attn(_p(qkv), i64((Hq + 2 * Hkv) * 64 if ldqkv is None else ldqkv), B, Hq, Hkv, 64, _p(inv_freq), _p(rope_tab),
+                                 _p(pos), _p(kc), _p(vc), _p(block_table), block_table.shape[1], page, C.c_float(0.125), _p(out),
+                                 i64(Hq * 64 if ldo is None else ldo), dtype, int(bool(out_packed)) | (2 if per_head else 0) | (8 if out_split == "f16" else (4 if out_split else 0)) | (16 if one_head else 0), stream()), "mmx_decode_attn")
 
 
 def swiglu(gu, out, *, rows, I, dtype, ldgu=None, ldo=None):

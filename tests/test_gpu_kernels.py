@@ -439,7 +439,8 @@ def test_decode_attn_one_token(env, dt, per_head, ctx):
         ops.decode_attn(qkv, inv, pos, kc, vc, bt, out, B=B, Hq=Hq, Hkv=Hkv, page=page, dtype=dt, out_packed=packed,
                         per_head=per_head, rope_tab=tab)
         got = ops.unpack_act(out, B, Hq * D, dt).float().cpu() if packed else out[:B].float().cpu()
-        if dt == 0 or per_head:                            # two query heads per workgroup (the default) = one per workgroup, bit for bit
+        if dt == 0 or per_head:                            # one_head=True changes nothing here: B * Hq = 70 <= 256 launches one head per
+            # workgroup anyway (the two-heads kernel against this one: test_gpu_kv_parity.py::test_decode_attn_two_heads_per_workgroup)
             kc1, vc1, out1 = kc0.clone(), vc0.clone(), torch.zeros_like(out)
             ops.decode_attn(qkv, inv, pos, kc1, vc1, bt, out1, B=B, Hq=Hq, Hkv=Hkv, page=page, dtype=dt, out_packed=packed,
                             per_head=per_head, rope_tab=tab, one_head=True)
