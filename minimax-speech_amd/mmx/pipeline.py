@@ -6,7 +6,10 @@ vocoder call (model.py:316) replaced by DACVAE.decode, as the README pipeline an
 (speech_latent, flow.py:388-389) imply.
 """
 import os
+import queue
+import threading
 import time
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import torch
@@ -16,9 +19,20 @@ from ._lib import BF16, F32, TORCH_DT, X2, X3, is_split
 from .dac import DacDecoderEngine
 from .flow import FlowEngine, Graphed
 from .llm import ST_FIN, ST_NOUT, ST_POS, LlmEngine
+from .sched import GroupScheduler, groups
 
 TOKEN_RATE = 25          # FSQ tokens per second (config.yaml:12)
 SAMPLE_RATE = 24000
+
+
+def step_bounds(n_text, exact_steps, min_ratio=2, max_ratio=20):
+    """(min_len, max_len) of one decode: the text length times the ratios (llm.py:706-707), or exactly exact_steps with EOS ignored."""
+    return (exact_steps, exact_steps) if exact_steps is not None else (int(n_text * min_ratio), int(n_text * max_ratio))
+
+
+def _own(v, b):
+    """Utterance b's value of an optional per-utterance argument: None, one value for all, or a list (entries may be None)."""
+    return v[b] if isinstance(v, (list, tuple)) else v
 
 
 def fade_in_out(fade_in, fade_out, window):
@@ -110,32 +124,38 @@ class TtsEngine:
         """Batched AR decode (Qwen2LM.inference semantics per sequence). exact_steps (int or list) forces exactly
         that many sampling steps with EOS ignored (BASELINE config 3: 250 steps for a 10 s utterance).
         samplers / seeds: per utterance (LlmEngine.start); None = the LM engine's sampler attributes and the scalar `seed`."""
-        B = len(texts)
-        assert B == self.llm.B
-        if exact_steps is not None and not isinstance(exact_steps, (list, tuple)):
-            exact_steps = [exact_steps] * B
-        z = lambda: torch.zeros(1, 0, dtype=torch.long, device=self.dev)
-        xs, mins, maxs = [], [], []
-        for b in range(B):
-            pt = prompt_texts[b] if prompt_texts else z()
-            ps = prompt_speech[b] if prompt_speech else z()
-            xs.append(self.llm.build_lm_input(texts[b], pt, ps))
-            n = texts[b].numel()
-            mins.append(exact_steps[b] if exact_steps is not None else int(n * min_ratio))
-            maxs.append(exact_steps[b] if exact_steps is not None else int(n * max_ratio))
-        self.llm.start(xs, mins, maxs, seed=seed, samplers=samplers, seeds=seeds)
+        assert len(texts) == self.llm.B
+        xs = [self.llm.build_lm_input(t, self._prompt(_own(prompt_texts, b)), self._prompt(_own(prompt_speech, b)))
+              for b, t in enumerate(texts)]
+        mins, maxs = zip(*(step_bounds(t.numel(), _own(exact_steps, b), min_ratio, max_ratio) for b, t in enumerate(texts)))
+        self.llm.start(xs, list(mins), list(maxs), seed=seed, samplers=samplers, seeds=seeds)
         self.llm.run(max(maxs))
         return self.llm.accepted()
+
+    def _prompt(self, x, feat=False):
+        """A prompt argument, None = no prompt: zero tokens [1, 0] (text, LM / flow speech tokens) or, feat=True, latents [1, 0, 80]."""
+        if x is not None:
+            return x
+        return torch.zeros(1, 0, 80, device=self.dev) if feat else torch.zeros(1, 0, dtype=torch.long, device=self.dev)
+
+    def _latents2wav(self, lat):
+        """fp32 latents [T, 80] -> waveform [1, 1, T * hop]: copied into the compute dtype, then the DAC decoder.  A list of two or
+        more: ONE decode of the zero-padded group (DacDecoderEngine.decode_time_major with per-member lengths: row masks in the
+        GEMM epilogues, lengths in the fused ResidualUnits) instead of ~32 launches per utterance; member i of the result,
+        wav[i, :, :T_i * hop], equals its own decode bit for bit.  (One utterance passes no lengths: they only add mask launches.)"""
+        lats = list(lat) if isinstance(lat, (list, tuple)) else [lat]
+        Ts = [int(l.shape[0]) for l in lats]
+        alloc = torch.zeros if len(lats) > 1 else torch.empty            # padding rows are read: zero filled
+        zt = alloc(len(lats), max(Ts), 80, dtype=TORCH_DT[self.dtype], device=self.dev)
+        for i, l in enumerate(lats):
+            ops.copy2d(l.contiguous(), F32, 0, 80, 1, zt[i], self.dtype, 0, 80, 1, rows=Ts[i], cols=80)
+        return self.dac.decode_time_major(zt, len(lats), max(Ts), lens=(Ts if len(lats) > 1 else None))
 
     @torch.no_grad()
     def token2wav(self, token: torch.Tensor, prompt_token: torch.Tensor, prompt_feat: torch.Tensor,
                   embedding: torch.Tensor, streaming=False, finalize=True) -> torch.Tensor:
         """tokens [1,L] -> waveform [1, 1, 2*L*hop] (cli/model.py:285-319 with the vocoder swapped for DAC)."""
-        lat = self.flow.inference_time_major(token, prompt_token, prompt_feat, embedding, streaming, finalize)
-        T2 = lat.shape[0]
-        zt = torch.empty(1, T2, 80, dtype=TORCH_DT[self.dtype], device=self.dev)
-        ops.copy2d(lat, F32, 0, 80, 1, zt, self.dtype, 0, 80, 1, rows=T2, cols=80)
-        return self.dac.decode_time_major(zt, 1, T2)
+        return self._latents2wav(self.flow.inference_time_major(token, prompt_token, prompt_feat, embedding, streaming, finalize))
 
     @torch.no_grad()
     def reference_embedding(self, reference_audio, sample_rate=24000, cache=None) -> torch.Tensor:
@@ -166,13 +186,9 @@ class TtsEngine:
         """One utterance, non-streaming (cli/model.py:321-386 `stream=False` branch).  reference_audio (instead of
         flow_embedding): the voice as a recording, see reference_embedding."""
         flow_embedding = self._embedding_arg(flow_embedding, reference_audio, sample_rate)
-        z = torch.zeros(1, 0, dtype=torch.long, device=self.dev)
-        toks = self.generate_tokens([text], [prompt_text if prompt_text is not None else z],
-                                    [llm_prompt_speech_token if llm_prompt_speech_token is not None else z],
-                                    seed=seed, exact_steps=exact_steps)[0]
-        pf = prompt_speech_feat if prompt_speech_feat is not None else torch.zeros(1, 0, 80, device=self.dev)
-        pt = flow_prompt_speech_token if flow_prompt_speech_token is not None else z
-        return self.token2wav(toks.reshape(1, -1), pt, pf, flow_embedding)
+        toks = self.generate_tokens([text], [prompt_text], [llm_prompt_speech_token], seed=seed, exact_steps=exact_steps)[0]
+        return self.token2wav(toks.reshape(1, -1), self._prompt(flow_prompt_speech_token), self._prompt(prompt_speech_feat, feat=True),
+                              flow_embedding)
 
     MEL_CACHE = 8            # cli/model.py:258: frames of overlap between two passes
 
@@ -211,16 +227,9 @@ class TtsEngine:
         first hop."""
         assert self.llm.B == 1
         flow_embedding = self._embedding_arg(flow_embedding, reference_audio, sample_rate)
-        z = torch.zeros(1, 0, dtype=torch.long, device=self.dev)
-        zf = torch.zeros(1, 0, 80, device=self.dev)
-        pt = prompt_text if prompt_text is not None else z
-        lps = llm_prompt_speech_token if llm_prompt_speech_token is not None else z
-        fpt = flow_prompt_speech_token if flow_prompt_speech_token is not None else z
-        pf = prompt_speech_feat if prompt_speech_feat is not None else zf
-        x = self.llm.build_lm_input(text, pt, lps)
-        n_text = int(text.numel())
-        mn = exact_steps if exact_steps is not None else n_text * 2
-        mx = exact_steps if exact_steps is not None else n_text * 20
+        fpt, pf = self._prompt(flow_prompt_speech_token), self._prompt(prompt_speech_feat, feat=True)
+        x = self.llm.build_lm_input(text, self._prompt(prompt_text), self._prompt(llm_prompt_speech_token))
+        mn, mx = step_bounds(int(text.numel()), exact_steps)
         if not hasattr(self, "_lm_stream"):
             self._lm_stream = torch.cuda.Stream(device=self.dev, priority=-1)
         lm, caller = self._lm_stream, torch.cuda.current_stream()
@@ -257,10 +266,7 @@ class TtsEngine:
             ctx = None if tail is None else tail[:tail.shape[0] - re][-CL:]
             seg = lat[start:] if ctx is None or ctx.shape[0] == 0 else torch.cat([ctx, lat[start:]], dim=0)
             nctx = 0 if ctx is None else ctx.shape[0]
-            n = seg.shape[0]
-            zt = torch.empty(1, n, 80, dtype=TORCH_DT[self.dtype], device=self.dev)
-            ops.copy2d(seg.contiguous(), F32, 0, 80, 1, zt, self.dtype, 0, 80, 1, rows=n, cols=80)
-            wav = self.dac.decode_time_major(zt, 1, n)[:, 0, nctx * self.hop:(nctx + hi - start) * self.hop]
+            wav = self._latents2wav(seg)[:, 0, nctx * self.hop:(nctx + hi - start) * self.hop]
             lat_used = lat[emitted:hi]
             if finalize:
                 if re:
@@ -313,22 +319,6 @@ class TtsEngine:
         caller.wait_stream(lm)
 
     # ------------------------------------------------------------------ batch of independent utterances
-    def _groups(self, order, frames, group_size, max_pad_ratio, frame_quantum, first=0):
-        """Consecutive runs of `order` (sorted by length) whose lengths are within the padding budget.
-        group_size may be a list: the size limit of the k-th group issued (k counted from `first`); the last entry
-        repeats.  A ramp such as [2, 2, 4, 8] lets the flow stage start as soon as the two shortest utterances are
-        decoded instead of waiting for eight."""
-        sizes = group_size if isinstance(group_size, (list, tuple)) else [group_size]
-        out, i = [], 0
-        while i < len(order):
-            gs = sizes[min(first + len(out), len(sizes) - 1)]
-            j, t0 = i + 1, frames[order[i]]
-            while j < len(order) and j - i < gs and frames[order[j]] <= max(t0 * max_pad_ratio, t0 + frame_quantum):
-                j += 1
-            out.append(order[i:j])
-            i = j
-        return out
-
     def _flow_dac_group(self, grp, toks, embs, wavs, frame_quantum, flow=None, prompts=None):
         """Flow + DAC for a group of finished utterances: per-utterance conformer encoder, one batched ODE solve, per-
         utterance DAC decode.  prompts: per utterance (flow_prompt_speech_token [1, Lp], prompt_speech_feat [1, Tp, 80]) or
@@ -336,9 +326,7 @@ class TtsEngine:
         `cond` rows of its frames, and its frames are dropped from the result).
         MMX_TIMING=3 prints the three stage times (with stream syncs between them)."""
         flow = flow or self.flow
-        z = torch.zeros(1, 0, dtype=torch.long, device=self.dev)
-        zf = torch.zeros(1, 0, 80, device=self.dev)
-        pr = lambda b: (z, zf) if (prompts is None or prompts[b] is None) else prompts[b]
+        pr = [_own(prompts, b) or (self._prompt(None), self._prompt(None, feat=True)) for b in grp]
         trace = os.environ.get("MMX_TIMING") == "3"
         marks = []
 
@@ -380,36 +368,20 @@ class TtsEngine:
         mark()
         if self.batch_encoder and len(grp) > 1:
             # one encoder pass over the zero-padded group (FlowEngine.encode_batch)
-            conds = flow.conditions_batch([toks[b].reshape(1, -1) for b in grp], [pr(b)[0] for b in grp], [pr(b)[1] for b in grp],
+            conds = flow.conditions_batch([toks[b].reshape(1, -1) for b in grp], [p[0] for p in pr], [p[1] for p in pr],
                                           [embs[b] for b in grp])
         else:
-            conds = fanned([(lambda b=b: flow.conditions(toks[b].reshape(1, -1), pr(b)[0], pr(b)[1], embs[b])) for b in grp])
+            conds = fanned([(lambda b=b, p=p: flow.conditions(toks[b].reshape(1, -1), p[0], p[1], embs[b])) for b, p in zip(grp, pr)])
         mark()
         xs = flow.cfm_batch([c[0] for c in conds], [c[1] for c in conds], [c[2] for c in conds], pad_to=frame_quantum)
         mark()
-
-        def dac_job(b, lat, c):
-            lat = lat[c[3]:]                                 # the prompt's frames are not rendered (flow.py:509)
-            T2 = lat.shape[0]
-            zt = torch.empty(1, T2, 80, dtype=TORCH_DT[self.dtype], device=self.dev)
-            ops.copy2d(lat, F32, 0, 80, 1, zt, self.dtype, 0, 80, 1, rows=T2, cols=80)
-            return self.dac.decode_time_major(zt, 1, T2)
-
+        lats = [lat[c[3]:] for lat, c in zip(xs, conds)]     # the prompt's frames are not rendered (flow.py:509)
         if self.batch_dac and len(grp) > 1 and not aux:
-            # ONE decode of the zero-padded group (DacDecoderEngine.decode_time_major with per-member lengths: row masks in the
-            # GEMM epilogues, lengths in the fused ResidualUnits) instead of ~32 launches per utterance; member i of the result
-            # equals its own decode bit for bit
-            lats = [lat[c[3]:] for lat, c in zip(xs, conds)]
-            Ts = [int(l.shape[0]) for l in lats]
-            Tm = max(Ts)
-            zt = torch.zeros(len(grp), Tm, 80, dtype=TORCH_DT[self.dtype], device=self.dev)
-            for i, l in enumerate(lats):
-                ops.copy2d(l, F32, 0, 80, 1, zt[i], self.dtype, 0, 80, 1, rows=Ts[i], cols=80)
-            wav = self.dac.decode_time_major(zt, len(grp), Tm, lens=Ts)
+            wav = self._latents2wav(lats)                    # one decode of the zero-padded group
             for i, b in enumerate(grp):
-                wavs[b] = wav[i:i + 1, :, :Ts[i] * self.hop]
+                wavs[b] = wav[i:i + 1, :, :lats[i].shape[0] * self.hop]
         else:
-            for b, w in zip(grp, fanned([(lambda b=b, lat=lat, c=c: dac_job(b, lat, c)) for b, lat, c in zip(grp, xs, conds)])):
+            for b, w in zip(grp, fanned([(lambda l=l: self._latents2wav(l)) for l in lats])):
                 wavs[b] = w
         if aux:
             # blocks the auxiliary streams allocated (and this function's temporaries freed there) go back to THEIR pools:
@@ -451,53 +423,41 @@ class TtsEngine:
         reference_audio: per utterance, a recording of the voice (reference_embedding) used where flow_embeddings[b] would be
         (an entry of None keeps flow_embeddings[b]); every distinct clip object is embedded once, before the decode loop starts.
         polite: flow groups issued while the decode loop runs use FlowEngine.polite tiling (64-row tiles: fewer workgroups,
-        more of the chip left to the decode loop's launches); the groups of the final harvest use the fastest tiling.
+        more of the chip left to the decode loop's launches); the groups of the final poll use the fastest tiling.
         tail_active > 0: once at most that many sequences are still decoding, a finished utterance no longer waits for
         companions when a flow worker is (predicted) idle - the decode loop is the critical path, and whatever the last
         utterances still have to do after their last token is what the step ends on."""
-        import queue as queue_mod
-        import threading
         B = len(texts)
         if reference_audio is None and flow_embeddings is None:
             raise ValueError("give flow_embeddings or reference_audio")
         if reference_audio is not None:
             assert len(reference_audio) == B
-            seen = {}
-            if flow_embeddings is None:
-                flow_embeddings = [None] * B
-            flow_embeddings = [self._embedding_arg(flow_embeddings[b], None, sample_rate) if reference_audio[b] is None else
-                               self.reference_embedding(reference_audio[b], sample_rate, seen) for b in range(B)]
+            clips = {}                                    # one embedding per distinct clip object
+            flow_embeddings = [self._embedding_arg(_own(flow_embeddings, b), None, sample_rate) if clip is None else
+                               self.reference_embedding(clip, sample_rate, clips) for b, clip in enumerate(reference_audio)]
         NS = self.llm.B                                   # decode slots; more utterances than slots queue up and are admitted
         assert B >= NS and (overlap or B == NS)           # into slots as they free (continuous batching, LlmEngine.admit)
         assert (samplers is None or len(samplers) == B) and (seeds is None or len(seeds) == B)
-        own = lambda lst, b: None if lst is None else lst[b]
-        if exact_steps is not None and not isinstance(exact_steps, (list, tuple)):
-            exact_steps = [exact_steps] * B
-        z = torch.zeros(1, 0, dtype=torch.long, device=self.dev)
-        pick = lambda lst, b: z if (lst is None or lst[b] is None) else lst[b]
-        xs = [self.llm.build_lm_input(t, pick(prompt_texts, b), pick(llm_prompt_speech_tokens, b)) for b, t in enumerate(texts)]
-        prompts = None
-        if flow_prompt_speech_tokens is not None:
-            zf = torch.zeros(1, 0, 80, device=self.dev)
-            prompts = [None if flow_prompt_speech_tokens[b] is None else
-                       (flow_prompt_speech_tokens[b], zf if prompt_speech_feats is None or prompt_speech_feats[b] is None else prompt_speech_feats[b])
-                       for b in range(B)]
-        plen = [0 if (prompts is None or prompts[b] is None) else int(prompts[b][0].numel()) for b in range(B)]   # prompt tokens in the flow
-        mins = [exact_steps[b] if exact_steps is not None else int(texts[b].numel() * 2) for b in range(B)]
-        maxs = [exact_steps[b] if exact_steps is not None else int(texts[b].numel() * 20) for b in range(B)]
+        xs = [self.llm.build_lm_input(t, self._prompt(_own(prompt_texts, b)), self._prompt(_own(llm_prompt_speech_tokens, b)))
+              for b, t in enumerate(texts)]
+        prompts = flow_prompt_speech_tokens and [None if fp is None else (fp, self._prompt(_own(prompt_speech_feats, b), feat=True))
+                                                 for b, fp in enumerate(flow_prompt_speech_tokens)]
+        plen = [int(p[0].numel()) if p else 0 for p in prompts or [None] * B]                      # prompt tokens in the flow
+        mins, maxs = (list(v) for v in zip(*(step_bounds(t.numel(), _own(exact_steps, b)) for b, t in enumerate(texts))))
         wavs: List[Optional[torch.Tensor]] = [None] * B
         toks: List[Optional[torch.Tensor]] = [None] * B
+        self.last_tokens, self.last_schedule = toks, None    # accepted ids per utterance (device int64 tensors); GroupScheduler.log
         if not overlap:
             self.llm.start(xs, mins, maxs, seed=seed, samplers=samplers, seeds=seeds)
             self.llm.run(max(maxs), poll_every)
             n = self.llm.state[ST_NOUT].tolist()
             toks[:] = self.llm.accepted(n=n)
             order = sorted(range(B), key=lambda b: (n[b], b))
-            for grp in self._groups(order, [2 * (v + plen[b]) for b, v in enumerate(n)], group_size, max_pad_ratio, frame_quantum):
+            for grp in groups(order, [2 * (v + plen[b]) for b, v in enumerate(n)], group_size, max_pad_ratio, frame_quantum):
                 self._flow_dac_group(grp, toks, flow_embeddings, wavs, frame_quantum, prompts=prompts)
-            self.last_tokens = toks
             return wavs
 
+        # ---- start: flow workers, scheduler, decode loop
         if not hasattr(self, "_sides") or len(self._sides) != flow_workers:
             # the decode loop is a chain of short latency-bound kernels: give it the high-priority queue so its
             # launches are not parked behind the flow's large grids.  The flow stage itself is a chain of short
@@ -508,124 +468,42 @@ class TtsEngine:
             self._sides = [self._flow_stream() for _ in range(flow_workers)]
             self._flows = [self.flow] + [self.flow.clone_shared() for _ in range(flow_workers - 1)]
             self._hi = torch.cuda.Stream(device=self.dev, priority=-1)
-        qs, err = [queue_mod.Queue() for _ in range(flow_workers)], []
-        caller = torch.cuda.current_stream()
-        self._hi.wait_stream(caller)
+        qs, err = [queue.Queue() for _ in range(flow_workers)], []
+        caller, main = torch.cuda.current_stream(), self._hi
+        main.wait_stream(caller)
+        trace = os.environ.get("MMX_TIMING") == "2"
+        group_events: list = []
+        cold0 = Graphed.cold_calls
+        t0 = time.perf_counter()
 
         def worker(wi):
             side, flow = self._sides[wi], self._flows[wi]
             try:
                 torch.cuda.set_device(self.dev)
                 with torch.cuda.stream(side):
-                    while True:
-                        item = qs[wi].get()
-                        if item is None:
-                            return
-                        grp, ev, flow.polite = item
+                    for grp, ev, flow.polite in iter(qs[wi].get, None):
                         side.wait_event(ev)                      # the group's token ids were written on the LM stream
-                        t_in = _time.perf_counter()
+                        t_in = time.perf_counter()
                         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         e0.record(side)
                         self._flow_dac_group(grp, toks, flow_embeddings, wavs, frame_quantum, flow, prompts)
                         e1.record(side)                          # read after the call has drained: the scheduler's cost model
                         group_events.append((sum(2 * toks[b].numel() for b in grp), flow.polite, e0, e1))
-                        if _trace:
+                        if trace:
                             side.synchronize()
                             print(f"[tts_batch]   worker {wi}: group of {len(grp)} ({[2 * toks[b].numel() for b in grp]} frames) "
-                                  f"{(t_in - self._t0) * 1e3:.0f} -> {(_time.perf_counter() - self._t0) * 1e3:.0f} ms", flush=True)
+                                  f"{(t_in - t0) * 1e3:.0f} -> {(time.perf_counter() - t0) * 1e3:.0f} ms", flush=True)
             except BaseException as e:                           # surfaced by the caller
                 err.append(e)
 
-        _os, _time = os, time
-        _trace = os.environ.get("MMX_TIMING") == "2"
-        self._t0 = _time.perf_counter()
         ths = [threading.Thread(target=worker, args=(wi,), daemon=True) for wi in range(flow_workers)]
         for th in ths:
             th.start()
-        main = self._hi
-        pending: List[int] = []
-        seen = set()
-        issued = [0]
-        arrived, steps_done = {}, [1]
-        free_at = [0.0] * flow_workers
-        # the scheduler's cost model (self.sched): a decode step STEP_MS; a flow group GROUP_MS + FRAME_MS per frame - measured by
-        # every call for itself (_refit_sched) and, with sched_adapt, followed when two steady calls in a row say it is off by more
-        # than SCHED_HYSTERESIS (a steady workload keeps one assignment - and one set of captured plans - from call to call)
-        STEP_MS, GROUP_MS, FRAME_MS = self.sched["step_ms"], self.sched["group_ms"], self.sched["frame_ms"]
-        group_events: list = []
-        cold0 = Graphed.cold_calls
-
-        cur = [self.llm, list(range(NS))]                           # active engine, slot -> utterance index
-        waiting = list(range(NS, B))                                # utterances waiting for a slot
-
-        def harvest(final):
-            eng, slots = cur
-            fin = eng.state[ST_FIN].tolist()
-            n = eng.state[ST_NOUT].tolist()
-            new = sorted([s_ for s_ in range(len(slots)) if (fin[s_] or final) and slots[s_] not in seen],
-                         key=lambda s_: (n[s_], slots[s_]))
-            for s_, ids in zip(new, eng.accepted(new, n)):
-                b = slots[s_]
-                seen.add(b)
-                toks[b] = ids
-                pending.append(b)
-                arrived[b] = steps_done[0]
-            while waiting and not final:                            # a freed slot takes the next queued utterance
-                free = [s_ for s_ in range(len(slots)) if fin[s_] and slots[s_] in seen and slots[s_] >= 0]
-                if not free:
-                    break
-                s_, b = free[0], waiting.pop(0)
-                eng.admit(s_, xs[b], mins[b], maxs[b], seq_id=b, sampler=own(samplers, b), seed=own(seeds, b))   # reserves KV pages for the whole max_len
-                slots[s_] = b
-                fin[s_] = 0
-            if not final and eng is self.llm:
-                # every running sequence must own the pages the steps up to the next poll will write (a no-op when admit /
-                # start reserved the whole max_len; raises when the allocator is exhausted instead of decoding into the
-                # shared scratch page)
-                eng.ensure_capacity(poll_every + 1, pos=eng.state[ST_POS].tolist(),
-                                    active=[s_ for s_ in range(len(slots)) if not fin[s_]])
-            if (not final and not waiting and self.llm_small is not None and eng is self.llm and B - len(seen) <= self.llm_small.B
-                    and B - len(seen) > 0):
-                act = [s_ for s_ in range(len(slots)) if slots[s_] not in seen]
-                self.llm_small.compact_from(self.llm, act)
-                cur[0], cur[1] = self.llm_small, [slots[s_] for s_ in act]
-            frames = {b: 2 * (toks[b].numel() + plen[b]) for b in pending}
-            groups = self._groups(pending, frames, group_size, max_pad_ratio, frame_quantum, first=issued[0])
-            sizes = group_size if isinstance(group_size, (list, tuple)) else [group_size]
-            now = steps_done[0] * STEP_MS
-            if not final and groups:
-                want = sizes[min(issued[0] + len(groups) - 1, len(sizes) - 1)]
-                waited = steps_done[0] - min(arrived[b] for b in groups[-1])
-                rush = 0 < B - len(seen) <= tail_active and any(free_at[w] <= now for w in range(flow_workers))
-                if len(groups[-1]) < want and not (hold_steps > 0 and waited >= hold_steps) and not rush:
-                    groups = groups[:-1]                         # keep a partial group open for later arrivals
-            assign = None
-            if final and hold_steps > 0 and len(groups) == 1 and len(groups[0]) >= 2:
-                # last arrivals: longest first, each to the worker predicted to finish it first (the other worker may
-                # still be busy with an earlier group, then splitting only delays the end)
-                fa = [max(free_at[w], now) for w in range(flow_workers)]
-                parts = [[] for _ in range(flow_workers)]
-                for b in sorted(groups[0], key=lambda b: -frames[b]):
-                    w = min(range(flow_workers), key=lambda w: (fa[w] + (0.0 if parts[w] else GROUP_MS) + FRAME_MS * frames[b], w))
-                    fa[w] += (0.0 if parts[w] else GROUP_MS) + FRAME_MS * frames[b]
-                    parts[w].append(b)
-                assign = [w for w in range(flow_workers) if parts[w]]
-                groups = [sorted(parts[w], key=lambda b: (frames[b], b)) for w in assign]
-            for grp in groups:
-                ev = torch.cuda.Event()
-                ev.record(main)
-                # the worker predicted to be free first.  Prediction, not wall time: decode steps are the clock and a
-                # group costs GROUP_MS + FRAME_MS per frame (fitted to MMX_TIMING=2 traces), so the assignment - and
-                # with it every worker's set of captured plans - repeats from run to run
-                wi = assign.pop(0) if assign else min(range(flow_workers), key=lambda w: (max(free_at[w], now), w))
-                free_at[wi] = max(free_at[wi], now) + GROUP_MS + FRAME_MS * sum(frames[b] for b in grp)
-                # groups issued while the decode loop is running use the flow kernels' polite tiling (FlowEngine.polite);
-                # the last arrivals, issued when it has ended, the fastest one
-                qs[wi].put((grp, ev, polite and not final and B == NS))    # (with a queue the flow stage is the bottleneck)
-                issued[0] += 1
-                for b in grp:
-                    pending.remove(b)
-
+        sch = GroupScheduler(group_size, max_pad_ratio, frame_quantum, hold_steps, tail_active, flow_workers, self.sched, B, B == NS, polite)
+        self.last_schedule = sch.log
+        # eng, slots: the active engine and its slot -> utterance index; waiting: utterances without a slot yet
+        call = SimpleNamespace(eng=self.llm, slots=list(range(NS)), waiting=list(range(NS, B)), harvested=set(), toks=toks, plen=plen,
+                               sched=sch, qs=qs, main=main, B=B, poll_every=poll_every, xs=xs, mins=mins, maxs=maxs, samplers=samplers, seeds=seeds)
         with torch.cuda.stream(main):
             self.llm.start(xs[:NS], mins[:NS], maxs[:NS], seed=seed, samplers=samplers and samplers[:NS],
                            seeds=seeds and seeds[:NS])              # (captures serialise themselves: mmx/flow.py, Graphed)
@@ -634,22 +512,22 @@ class TtsEngine:
             # up to poll_every steps for its slot on top of its own max_len)
             done, max_steps = 1, (max(maxs) if B == NS else sum(maxs) + (B + 1) * poll_every)
             issue_s = 0.0                                        # host time spent enqueueing decode steps (graph replays)
-            while done < max_steps:
+            while done < max_steps:                              # ---- loop: k decode steps, then a poll
                 k = min(poll_every, max_steps - done)
-                t_i = _time.perf_counter()
+                t_i = time.perf_counter()
                 for _ in range(k):
-                    cur[0].step()
-                issue_s += _time.perf_counter() - t_i
+                    call.eng.step()
+                issue_s += time.perf_counter() - t_i
                 done += k
-                steps_done[0] = done
-                harvest(False)
-                if len(seen) == B:
+                self._poll_slots(call, self._poll_finished(call, done, False))
+                self._poll_issue(call, done, False)
+                if len(call.harvested) == B:
                     break
-            if waiting:
-                raise RuntimeError(f"tts_batch: {len(waiting)} queued utterances were never admitted")
-            harvest(True)
-        timing = os.environ.get("MMX_TIMING")
-        # The call returns finished audio, so it drains its streams on the host as well: the decode stream here, the
+            if call.waiting:
+                raise RuntimeError(f"tts_batch: {len(call.waiting)} queued utterances were never admitted")
+            self._poll_finished(call, done, True)                # ---- final poll: whatever is left arrives, nothing is held back
+            self._poll_issue(call, done, True)
+        # ---- drain.  The call returns finished audio, so it drains its streams on the host as well: the decode stream here, the
         # flow streams after the workers have issued everything.  Leaving the drain to stream waits (so that the next
         # call's decode loop is already queued behind them) measured 6 % slower per step: a blocked high-priority queue
         # ahead of the still running flow tail costs the tail more than the host round trip saves.
@@ -665,19 +543,60 @@ class TtsEngine:
             sd.synchronize()
         for fl in self._flows:
             fl.polite = False
-        if timing:
-            print(f"[tts_batch] LM loop done at {(t_lm - self._t0) * 1e3:.0f} ms, flow/DAC tail until {(time.perf_counter() - self._t0) * 1e3:.0f} ms, "
+        if os.environ.get("MMX_TIMING"):
+            print(f"[tts_batch] LM loop done at {(t_lm - t0) * 1e3:.0f} ms, flow/DAC tail until {(time.perf_counter() - t0) * 1e3:.0f} ms, "
                   f"decode steps {done}", flush=True)
         for sd in self._sides:
             caller.wait_stream(sd)
         caller.wait_stream(main)
-        self.last_tokens = toks                          # accepted ids per utterance (device int64 tensors)
         # host-side accounting of the call (bench.py puts it into its JSON line: a multi-GPU node runs N x (decode thread + flow
         # workers) on shared cores, and a slow host shows up here first)
-        self.last_host = dict(decode_steps=done, lm_issue_ms=round(issue_s * 1e3, 2), lm_done_ms=round((t_lm - self._t0) * 1e3, 1),
-                              call_ms=round((time.perf_counter() - self._t0) * 1e3, 1))
-        self._refit_sched(done, (t_lm - self._t0) * 1e3, group_events, steady=(Graphed.cold_calls == cold0 and B == NS))
+        self.last_host = dict(decode_steps=done, lm_issue_ms=round(issue_s * 1e3, 2), lm_done_ms=round((t_lm - t0) * 1e3, 1),
+                              call_ms=round((time.perf_counter() - t0) * 1e3, 1))
+        self._refit_sched(done, (t_lm - t0) * 1e3, group_events, steady=(Graphed.cold_calls == cold0 and B == NS))
         return wavs
+
+    def _poll_finished(self, call, step, final):
+        """A poll of tts_batch's decode loop (`call`: that call's state), step 1: reads the finished flags once; the utterances that
+        finished since the last poll (at the final one: all that are left) arrive at the scheduler, shortest first.  Returns the flags."""
+        eng, slots = call.eng, call.slots
+        fin = eng.state[ST_FIN].tolist()
+        n = eng.state[ST_NOUT].tolist()
+        new = sorted([s_ for s_ in range(len(slots)) if (fin[s_] or final) and slots[s_] not in call.harvested],
+                     key=lambda s_: (n[s_], slots[s_]))
+        for s_, ids in zip(new, eng.accepted(new, n)):
+            b = slots[s_]
+            call.harvested.add(b)
+            call.toks[b] = ids
+            call.sched.arrive(b, 2 * (ids.numel() + call.plen[b]), step)
+        return fin
+
+    def _poll_slots(self, call, fin):
+        """Step 2, the slots: queued utterances into freed slots, KV pages for the steps up to the next poll, and the move into
+        the 16-slot engine once few enough sequences are left."""
+        eng, slots, harvested = call.eng, call.slots, call.harvested
+        for s_ in range(len(slots)):                            # a freed slot takes the next queued utterance
+            if call.waiting and fin[s_] and slots[s_] in harvested:
+                b = call.waiting.pop(0)
+                eng.admit(s_, call.xs[b], call.mins[b], call.maxs[b], seq_id=b, sampler=_own(call.samplers, b),
+                          seed=_own(call.seeds, b))             # reserves KV pages for the whole max_len
+                slots[s_], fin[s_] = b, 0
+        if eng is self.llm:
+            # every running sequence must own the pages the steps up to the next poll will write (a no-op when admit /
+            # start reserved the whole max_len; raises when the allocator is exhausted instead of decoding into the
+            # shared scratch page)
+            eng.ensure_capacity(call.poll_every + 1, pos=eng.state[ST_POS].tolist(), active=[s_ for s_ in range(len(slots)) if not fin[s_]])
+        if not call.waiting and self.llm_small is not None and eng is self.llm and 0 < call.B - len(harvested) <= self.llm_small.B:
+            act = [s_ for s_ in range(len(slots)) if slots[s_] not in harvested]
+            self.llm_small.compact_from(self.llm, act)
+            call.eng, call.slots = self.llm_small, [slots[s_] for s_ in act]
+
+    def _poll_issue(self, call, step, final):
+        """Step 3: the groups the scheduler issues now, each behind an event on the decode stream, onto their workers' queues."""
+        for _, wi, pol, grp in call.sched.issue(step, call.B - len(call.harvested), final):
+            ev = torch.cuda.Event()
+            ev.record(call.main)
+            call.qs[wi].put((grp, ev, pol))
 
     SCHED_HYSTERESIS = 0.25
     sched_adapt = False       # True: self.sched follows the measured fit (off by default: a change of the model moves groups between

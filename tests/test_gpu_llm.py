@@ -10,6 +10,13 @@ pytestmark = pytest.mark.gpu
 SEED = 7
 
 
+def recorded_schedule(golden_dir, name):
+    """The (step, worker, polite, group) list tts_batch issued in the recorded call `name` (tests/golden/sched.json)."""
+    import json
+    with open(os.path.join(golden_dir, "sched.json")) as f:
+        return [(step, wi, pol, grp) for step, wi, pol, grp in next(c for c in json.load(f) if c["name"] == name)["issued"]]
+
+
 @pytest.fixture(scope="module")
 def llm_sd(golden_dir):
     from oracle import weights as W
@@ -112,6 +119,7 @@ def test_overlapped_batch_pipeline_equals_sequential(golden_dir):
     for rep in range(3):       # eager warm-up, capture, replay
         got = eng.tts_batch(texts, emb, seed=3, exact_steps=lens, group_size=2, overlap=True)
         torch.cuda.synchronize()
+        assert eng.last_schedule == recorded_schedule(golden_dir, "overlapped6"), rep
         for a, b in zip(got, ref):
             assert a.shape == b.shape and (a - b).abs().max().item() < 2e-2, (rep, (a - b).abs().max().item())
 
@@ -227,7 +235,7 @@ def test_continuous_batching_equals_per_request_decode(llm_sd, dt):
         assert eng.pages.n_free == 14 and all(not p for p in eng.slot_pages)
 
 
-def test_tts_batch_with_more_utterances_than_slots():
+def test_tts_batch_with_more_utterances_than_slots(golden_dir):
     """tts_batch on a 3-slot engine with 7 utterances (the rest queue and are admitted as slots free) returns the
     waveforms of the 7-slot run (fp32 build, reduced-depth models): same ids, same audio."""
     from mmx import shapes, synth
@@ -248,6 +256,7 @@ def test_tts_batch_with_more_utterances_than_slots():
     for rep in range(2):
         got = e3.tts_batch(texts, emb, seed=3, exact_steps=lens, group_size=2, poll_every=4)
         torch.cuda.synchronize()
+        assert e3.last_schedule == recorded_schedule(golden_dir, "queue7on3"), rep
         assert [t.tolist() for t in e3.last_tokens] == want, rep
         for a, b in zip(got, ref):
             assert a.shape == b.shape and (a - b).abs().max().item() < 1e-4, (rep, a.shape, b.shape)
@@ -255,4 +264,5 @@ def test_tts_batch_with_more_utterances_than_slots():
     e1 = TtsEngine(llm_sd, flow_sd, dac_sd, dtype=0, max_batch=1, max_ctx=256)
     got = e1.tts_batch(texts[:3], emb[:3], seed=3, exact_steps=lens[:3], group_size=2, poll_every=4)
     torch.cuda.synchronize()
+    assert e1.last_schedule == recorded_schedule(golden_dir, "queue3on1")
     assert [t.tolist() for t in e1.last_tokens] == want[:3]
