@@ -461,7 +461,8 @@ int mmx_est_resnet(const MmxEstResnetParams* p, int dtype, int bm, int cfg, hipS
  * fp32 (MMX_X2), same strides.  w7 / w1: mmx_pack_skinny packs of the weight matrices [C][7 * CP] (tap-major, each tap's
  * C input channels zero-padded to CP = 32 * ceil(C / 32)) and [C][CP].  lens (optional, int32 [B]): rows >= lens[b] of batch
  * member b are conv padding - read as zero, written as zero (utterances of different lengths decoded in one batch).
- * bm: rows per workgroup, 0 = the library's default for (C, dtype). */
+ * bm: rows per workgroup, 0 = the library's default for (C, dtype); a height the build has no instantiation for is MMX_EARG
+ * (MMX_X2W has the default tile only). */
 typedef struct {
     const float* x;
     float* x_out;

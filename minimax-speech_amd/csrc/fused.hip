@@ -1469,7 +1469,8 @@ extern "C" int mmx_dac_ru(const MmxDacRuParams* pp, int dtype, int bm, hipStream
         MMX_LDS_OPT_IN((dac_ru_kernel<C_, BM_, WR_, WC_, NS_, PF_ __VA_OPT__(,) __VA_ARGS__>), lds);       \
         hipLaunchKernelGGL((dac_ru_kernel<C_, BM_, WR_, WC_, NS_, PF_ __VA_OPT__(,) __VA_ARGS__>), dim3((p.T + BM_ - 1) / BM_, p.B), dim3(256), lds, stream, p); \
     } while (0)
-    if (wplanes) {                                     // weight planes: the split build's default tile per stage
+    if (wplanes) {                                     // weight planes: the split build's default tile per stage, and no other
+        if (bm != 0 && bm != (p.C == 48 ? 64 : p.C == 96 ? (p.dil > 3 ? 128 : 64) : 32)) return MMX_EARG;
         if (p.C == 48) DACRU(48, 64, 4, 1, 2, 2, true);
         else if (p.C == 96) { if (p.dil > 3) DACRU(96, 128, 2, 2, 2, 3, true); else DACRU(96, 64, 2, 2, 2, 3, true); }
         else DACRU(192, 32, 1, 4, 2, 2, true);

@@ -242,13 +242,14 @@ def est_next(wqkv=None, n1g=None, n1b=None, q_out=None, ldq=0, q_bs=0, vt_out=No
 
 
 def est_tail(ao, x, w, *, B, T, dtype, bm, rowmask=None, act_out=None, act_ld=0, nxt=None, eps=1e-5, pf=0, t_begin=0,
-             Tcap=None, waves=0, occ2=False, narrow=False):
+             Tcap=None, waves=0, occ2=False, narrow=False, ldao=512):
     """w: dict with packed wo_p / w1_p / w2_p and bo / b1 / b2 / n3g / n3b (mmx/flow.py).  Tcap: frames every buffer is
-    allocated for (batch stride; default T); t_begin: first frame to process (streaming hop)."""
+    allocated for (batch stride; default T); t_begin: first frame to process (streaming hop); ldao: row pitch of ao (512 columns
+    are read)."""
     Tc = T if Tcap is None else Tcap
     p = L.fill_struct(L.EstTailParams(), ao=ao, x=x, wo=w["wo_p"], w1=w["w1_p"], w2=w["w2_p"], bo=w["bo"], b1=w["b1"],
-                      b2=w["b2"], n3g=w["n3g"], n3b=w["n3b"], rowmask=rowmask, act_out=act_out, ao_bs=Tc * 512,
-                      x_bs=Tc * 256, rm_bs=Tc, act_bs=Tc * act_ld, ldao=512, act_ld=act_ld, B=B, T=T, t_begin=t_begin, eps=eps)
+                      b2=w["b2"], n3g=w["n3g"], n3b=w["n3b"], rowmask=rowmask, act_out=act_out, ao_bs=Tc * ldao,
+                      x_bs=Tc * 256, rm_bs=Tc, act_bs=Tc * act_ld, ldao=ldao, act_ld=act_ld, B=B, T=T, t_begin=t_begin, eps=eps)
     if nxt is not None:
         p.next = nxt
     if isinstance(w["wo_p"], Planed):                   # [hi pack | lo pack] weights (pack_skinny with X2W), the next block's too
