@@ -104,7 +104,7 @@ int mmx_gemm_win_tile(const MmxGemmParams* p, int dtype, int tile, hipStream_t s
 /* ---------------------------------------------------------------------------------------------
  * Row-wise normalisation (LayerNorm / RMSNorm) with fused tail:
  *   y = norm(x[b][t][:]) * gamma (+ beta);  y = act(y);  y = (y*rowmask + addvec[b][:]) * rowmask
- * written to out_f32 and/or out_act (T).  rms != 0 selects RMSNorm (no mean, beta ignored).
+ * written to out_f32 and/or out_act (T).  rms != 0 selects RMSNorm (no mean, beta ignored).  C <= 2048.
  * Replaces nn.LayerNorm (+Mish, + time-embedding add) of decoder.py:65-85 / matcha decoder.py:56-61,
  * transformer.py norm1/norm3, encoder_layer.py norm_mha/norm_ff, Qwen2 RMSNorm (prefill).
  */
@@ -505,6 +505,52 @@ int mmx_dac_ru(const MmxDacRuParams* p, int dtype, int bm, hipStream_t stream);
 int mmx_logmel(const float* wave, int64_t w_bs, int L, int B, const float* gain, const int32_t* lens, const int32_t* h_lens,
                const void* basis, const void* filt, int n_fft, int hop, int bin0, int n_bins, int n_mels, float* out_cm,
                int64_t ldo, void* out_tm, int T, int dtype, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The S3 speech tokenizer's own kernels (speech/tools/S3Tokenizer/s3tokenizer, class S3TokenizerV2; cli/frontend.py:92-102).  Its
+ * convolutions, LayerNorms, projections, MLP and attention run on mmx_gemm_win (row_stride 2), mmx_rownorm and
+ * mmx_attn_flash_x / mmx_attn_dense.
+ *
+ * mmx_logmel_w: 16 kHz clip -> Whisper-convention log-mel (s3tokenizer/utils.py:220-267 log_mel_spectrogram): torch.stft with
+ * center=True (reflect padding by n_fft / 2 on each side) and a periodic Hann window, the last frame dropped (a member of len
+ * samples has len / hop frames), the POWER spectrum re^2 + im^2, the mel filterbank, log10(max(v, 1e-10)), the floor at
+ * (maximum over the whole clip) - 8, then (v + 4) / 4.  Arguments and tables as for mmx_logmel, except:
+ *   n_fft needs to be a multiple of 16 only (400): the K dimension of the basis is zero padded to kp = n_fft rounded up to 32,
+ *   basis bf16 [3][2 * nbp][kp]; the frame itself is not changed;
+ *   there is no gain.
+ * Two launches: the first writes the log10 values (and 0 for the frames t >= len / hop of a member), the second - one workgroup
+ * per clip - takes the maximum over the clip's own valid frames and applies the floor and the affine map to them.  A maximum
+ * has no order and a wave owns whole column tiles, so a member of a zero-padded batch gets the bits of its solo run.
+ *   out_cm fp32 [B][n_mels][ldo >= T] and / or out_tm T [B][T][n_mels]; a bf16 out_tm needs out_cm beside it (the maximum is
+ *   taken over the fp32 values).
+ * MMX_EARG: as mmx_logmel; a member with at most n_fft / 2 samples (the reflection is undefined; torch raises there too).
+ */
+int mmx_logmel_w(const float* wave, int64_t w_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, const void* basis,
+                 const void* filt, int n_fft, int hop, int bin0, int n_bins, int n_mels, float* out_cm, int64_t ldo,
+                 void* out_tm, int T, int dtype, hipStream_t stream);
+
+/* mmx_s3_rope_fsmn: what FSMNMultiHeadAttention.qkv_attention does between the projections and the softmax
+ * (s3tokenizer/model_v2.py:51-70 apply_rotary_emb, :177-189 forward_fsmn, :204-207), in one launch, fp32:
+ *   qkv  fp32 [B][T][ldqkv >= 3C] = [Q | K | V] of the fused projection, heads of 64 channels (C a multiple of 64).  Q and K are
+ *        rotated IN PLACE: y[d] = x[d] * cos[t][d % 32] + (d < 32 ? -x[d + 32] : x[d - 32]) * sin[t][d % 32], position t = the row
+ *        index, evaluated unfused as torch does; the reference's two D^-1/4 factors are the attention's scale = D^-1/2.
+ *   rope_cos / rope_sin fp32 [rope_rows >= T][32]: the real and imaginary parts of precompute_freqs_cis(64, 2048), built on the
+ *        host with the reference's own torch calls (no device trigonometry);
+ *   wt   fp32 [31][C]: fsmn_block.weight [C][1][31] transposed (tap-major);  x fp32 [B][T][C]: the block's input (residual);
+ *   r    fp32 [B][T][C] = x + (depthwise31(v m) + v m) m, m = (t < lens[b]); zero padding 15 / 15, the 31 taps summed in tap
+ *        order.  The out-projection's `residual` epilogue then finishes x + out(attn) + fsmn.
+ *   lens int32 [B] or NULL (= T): rows t >= lens[b] get r = x (bit for bit) and zero q / k, and their v is read as zero.
+ * One wave per (head, 32-row time tile): lane = channel, the RoPE partner is lane ^ 32, the tile's v rows and their halo in LDS. */
+int mmx_s3_rope_fsmn(float* qkv, int64_t ldqkv, int64_t qkv_bs, int B, int T, int C, const float* x, int64_t x_bs, float* r,
+                     int64_t r_bs, const float* wt, const float* rope_cos, const float* rope_sin, int rope_rows,
+                     const int32_t* lens, hipStream_t stream);
+
+/* mmx_fsq_encode: FSQCodebook.encode (s3tokenizer/model_v2.py:96-112): per row of x fp32 [B][T][ldx >= C]
+ *   h = W x + bias (W fp32 [8][C] = project_down.weight as loaded, fp32 dot products);  v_i = tanhf(h_i) * 0.9990000128746033f;
+ *   ids[b][t] = sum_i (rintf(v_i) + 1) * 3^i  (round half to even, digits in {0, 1, 2}, id in [0, 6561)), int32 [B][ld_ids >= T];
+ *   pre (optional) fp32 [B][T][8] receives the v_i.  lens int32 [B] or NULL: rows t >= lens[b] get id 0 (and v = 0). */
+int mmx_fsq_encode(const float* x, int64_t ldx, int64_t x_bs, int B, int T, int C, const float* W, const float* bias,
+                   const int32_t* lens, int32_t* ids, int64_t ld_ids, float* pre, hipStream_t stream);
 
 #ifdef __cplusplus
 }

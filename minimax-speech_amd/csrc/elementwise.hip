@@ -4,7 +4,8 @@
 #include "../../include/mmx_hip.h"
 
 // ---------------------------------------------------------------------------- rownorm
-// one wave per row; C <= 1024*? handled by a strided loop. fp32 statistics (two-pass over registers).
+// one wave per row, the row in registers (C <= 64 * MAXV; 2048 at most: the speech tokenizer's 1280 channels take MAXV = 32).
+// fp32 statistics (two-pass over registers).
 template <typename T, int MAXV, int ACT>
 __global__ __launch_bounds__(256) void rownorm_kernel(
     const float* __restrict__ x, long ldx, long x_bs, int rows, int C,
@@ -56,14 +57,14 @@ extern "C" int mmx_rownorm(const float* x, int64_t ldx, int64_t x_bstride, int r
                            float* out_f32, int64_t ldo_f, int64_t of_bstride,
                            void* out_act, int64_t ldo_a, int64_t oa_bstride, int dtype, hipStream_t stream) {
     dtype = MMX_ACT_DTYPE(dtype);
-    MMX_CHECK_ARG(x && gamma && rows > 0 && C > 0 && C <= 1024 && batch > 0 && (out_f32 || out_act));
+    MMX_CHECK_ARG(x && gamma && rows > 0 && C > 0 && C <= 2048 && batch > 0 && (out_f32 || out_act));
     dim3 grid((rows + 3) / 4, batch);
     MMX_CHECK_ARG(act == ACT_NONE || act == ACT_MISH);
 #define RN2(T, MV, A) hipLaunchKernelGGL((rownorm_kernel<T, MV, A>), grid, dim3(256), 0, stream, x, ldx, x_bstride, rows, C, \
         gamma, beta, eps, rms, act, rowmask, rm_bstride, addvec, av_bstride, out_f32, ldo_f, of_bstride, (T*)out_act, ldo_a, oa_bstride)
 #define RN(T, MV) do { if (act == ACT_MISH) RN2(T, MV, ACT_MISH); else RN2(T, MV, ACT_NONE); } while (0)
-    if (dtype == MMX_BF16) { if (C <= 256) RN(bf16_t, 4); else if (C <= 512) RN(bf16_t, 8); else RN(bf16_t, 16); }
-    else if (dtype == MMX_F32) { if (C <= 256) RN(float, 4); else if (C <= 512) RN(float, 8); else RN(float, 16); }
+    if (dtype == MMX_BF16) { if (C <= 256) RN(bf16_t, 4); else if (C <= 512) RN(bf16_t, 8); else if (C <= 1024) RN(bf16_t, 16); else RN(bf16_t, 32); }
+    else if (dtype == MMX_F32) { if (C <= 256) RN(float, 4); else if (C <= 512) RN(float, 8); else if (C <= 1024) RN(float, 16); else RN(float, 32); }
     else return MMX_EARG;
 #undef RN
 #undef RN2

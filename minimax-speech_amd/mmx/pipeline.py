@@ -46,7 +46,8 @@ def fade_in_out(fade_in, fade_out, window):
 
 class TtsEngine:
     def __init__(self, llm_sd, flow_sd, dac_sd, dtype=BF16, device="cuda", max_batch=1, max_ctx=2048,
-                 dac_rates=(5, 4, 4, 3, 2), use_graphs=True, attn="bf16", wplanes=False):
+                 dac_rates=(5, 4, 4, 3, 2), use_graphs=True, attn="bf16", wplanes=False, s3tok_sd=None, dacenc_sd=None,
+                 dacenc_rates=(2, 3, 4, 4, 5)):
         """wplanes (split build only): the weight-plane mode for checkpoints whose weights are NOT bf16-representable - what the
         reference's loaders hand over (fp32 llm.pt / flow.pt, cli/model.py:67-75; trained weight norms, dac-vae/inference.py:42-46).
         Every GEMM weight is carried as bf16 planes of its fp32 value (3 in the LM, 2 in the flow and the DAC: include/mmx_hip.h
@@ -69,6 +70,9 @@ class TtsEngine:
         self.flow = FlowEngine(flow_sd, dtype=dtype, device=device, use_graphs=use_graphs, attn=attn, wplanes=self.wplanes)
         self.dac = DacDecoderEngine(dac_sd, list(dac_rates), dtype=dtype, device=device, wplanes=self.wplanes)
         self.hop = self.dac.hop
+        # zero-shot prompts from a raw clip (prompt_from_audio): the S3 speech tokenizer and the DAC-VAE encoder, built on first use
+        self._s3tok_sd, self._dacenc_sd, self._dacenc_rates = s3tok_sd, dacenc_sd, list(dacenc_rates)
+        self._s3tok = self._dacenc = None
         # tts_batch's cost model of its own stages (ms): a decode step beside the flow; a flow group = group_ms + frame_ms per frame.
         # Initial values: what _refit_sched measures for this build on one MI355X on the config-4 share (it re-measures them in
         # every call: self.sched_fit; sched_adapt lets the model follow the fit)
@@ -174,6 +178,50 @@ class TtsEngine:
         if cache is not None:
             cache[key] = (reference_audio, e)              # the clip is kept alive with its id
         return e
+
+    @property
+    def s3tok(self):
+        """The speech tokenizer engine of `s3tok_sd` (mmx/s3tok.py), built on first use."""
+        if self._s3tok is None:
+            if self._s3tok_sd is None:
+                raise RuntimeError("prompt_from_audio needs the speech tokenizer: pass s3tok_sd (a state dict with S3TokenizerV2's keys)")
+            from .s3tok import SpeechTokenizerEngine
+            # weight planes are resolved from the tokenizer's own weights (its real checkpoint is fp32) unless they are forced on
+            self._s3tok = SpeechTokenizerEngine(self._s3tok_sd, dtype=self.dtype, device=self.dev,
+                                                wplanes=True if self.wplanes is True else None)
+        return self._s3tok
+
+    @property
+    def dacenc(self):
+        """The DAC-VAE encoder engine of `dacenc_sd`, built on first use."""
+        if self._dacenc is None:
+            if self._dacenc_sd is None:
+                raise RuntimeError("prompt_from_audio needs the DAC-VAE encoder: pass dacenc_sd (encoder.* and en_conv_post.* weights)")
+            from .dac import DacEncoderEngine
+            self._dacenc = DacEncoderEngine(self._dacenc_sd, self._dacenc_rates, dtype=self.dtype, device=self.dev)
+        return self._dacenc
+
+    @torch.no_grad()
+    def prompt_from_audio(self, wave16k, wave24k, prompt_text=None, noise=None, generator=None) -> dict:
+        """A zero-shot prompt from one recording given at both rates (mono [n] / [1, n] on the device; resampling stays with the
+        caller): frontend_zero_shot's speech part (cli/frontend.py:157-174).  wave16k -> speech tokens (the S3 tokenizer), wave24k
+        -> prompt latents (DACVAE.encode's z, as processor.py:149-159 reads them; `noise` / `generator` as DacEncoderEngine.encode)
+        and, where the flow has its speaker encoder, the embedding.  token_len = min(latent frames // 2, tokens); tokens are cut
+        to token_len and the latents to 2 * token_len.  The result splats into tts / tts_stream:
+        eng.tts(text, **eng.prompt_from_audio(w16, w24, prompt_text)) (pass flow_embedding= beside it when the flow has no
+        speaker encoder)."""
+        w24 = wave24k.to(self.dev, torch.float32).reshape(1, 1, -1)
+        tok = self.s3tok.tokenize([wave16k.to(self.dev)])[0]
+        z = self.dacenc.encode(torch.clamp(w24, -1.0, 1.0), noise=noise, generator=generator)[0]          # [1, 80, T']
+        token_len = min(z.shape[2] // 2, tok.numel())
+        tok = tok[:token_len].to(torch.long).reshape(1, -1)
+        out = {"llm_prompt_speech_token": tok, "flow_prompt_speech_token": tok,
+               "prompt_speech_feat": z[:, :, :2 * token_len].transpose(1, 2).contiguous()}
+        if prompt_text is not None:
+            out["prompt_text"] = prompt_text
+        if self.flow.spk_enc is not None:
+            out["flow_embedding"] = self.reference_embedding(w24.reshape(-1), 24000)
+        return out
 
     def _embedding_arg(self, flow_embedding, reference_audio, sample_rate):
         if (flow_embedding is None) == (reference_audio is None):

@@ -195,3 +195,33 @@ def llm_manifest(vocab=151936, hidden=896, inter=4864, layers=24, heads=14, kv_h
     m["spk_embed_affine_layer.weight"] = (hidden, spk_embed_dim)
     m["spk_embed_affine_layer.bias"] = (hidden,)
     return m
+
+
+def s3tok_manifest(C=1280, heads=20, layers=6, n_mels=128) -> Manifest:
+    """speech/tools/S3Tokenizer/s3tokenizer/model_v2.py: S3TokenizerV2 = AudioEncoderV2 (:290-318; two k3 convs, `layers`
+    ResidualAttentionBlock with FSMNMultiHeadAttention, :152-175,252-273) + FSQCodebook.project_down (:85-87).  4 + 16 * layers
+    + 2 keys; `heads` does not show in a shape (the head dimension is 64 whatever it is: freqs_cis is built for 64)."""
+    assert C == 64 * heads, "the reference's rotary table fixes the head dimension at 64"
+    m: Manifest = {"encoder.conv1.weight": (C, n_mels, 3), "encoder.conv1.bias": (C,),
+                   "encoder.conv2.weight": (C, C, 3), "encoder.conv2.bias": (C,)}
+    for i in range(layers):
+        p = f"encoder.blocks.{i}"
+        m[p + ".attn.query.weight"] = (C, C)
+        m[p + ".attn.query.bias"] = (C,)
+        m[p + ".attn.key.weight"] = (C, C)
+        m[p + ".attn.value.weight"] = (C, C)
+        m[p + ".attn.value.bias"] = (C,)
+        m[p + ".attn.out.weight"] = (C, C)
+        m[p + ".attn.out.bias"] = (C,)
+        m[p + ".attn.fsmn_block.weight"] = (C, 1, 31)
+        m[p + ".attn_ln.weight"] = (C,)
+        m[p + ".attn_ln.bias"] = (C,)
+        m[p + ".mlp.0.weight"] = (4 * C, C)
+        m[p + ".mlp.0.bias"] = (4 * C,)
+        m[p + ".mlp.2.weight"] = (C, 4 * C)
+        m[p + ".mlp.2.bias"] = (C,)
+        m[p + ".mlp_ln.weight"] = (C,)
+        m[p + ".mlp_ln.bias"] = (C,)
+    m["quantizer._codebook.project_down.weight"] = (8, C)
+    m["quantizer._codebook.project_down.bias"] = (8,)
+    return m

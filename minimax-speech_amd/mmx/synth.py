@@ -1,4 +1,4 @@
-"""Deterministic synthetic ("random-init") weights for the three hot-path models.
+"""Deterministic synthetic ("random-init") weights for the hot-path models and the speech tokenizer.
 
 No pretrained weights exist offline, so benchmarks and tests run on random-init weights of the right
 architecture (BASELINE.json).  Every tensor is a pure function of (state-dict key, shape, seed) on torch's CPU
@@ -76,6 +76,19 @@ def _synth_tensor(name: str, shape: Tuple[int, ...], seed: int) -> torch.Tensor:
         return _randn(shape, g, _wn_gain(n, shape) / math.sqrt(fan))
     if n.endswith(".weight_g"):
         raise KeyError("weight_g is derived from weight_v: use synth_state_dict")
+    # ---- S3 speech tokenizer (s3tok_manifest): LayerNorms named *_ln; the branches added to the residual stream (attention
+    # out-projection, FSMN memory, MLP output) damped so that the hidden state's rms stays O(1) through the stack; project_down
+    # scaled so that tanh(h) is spread over all three FSQ digits
+    if n.startswith("encoder.blocks.") and ("attn_ln." in n or "mlp_ln." in n):
+        return _randn(shape, g, 0.1, 1.0) if n.endswith("weight") else _randn(shape, g, 0.05)
+    if n.startswith("encoder.blocks.") and (n.endswith("attn.out.weight") or n.endswith("mlp.2.weight")):
+        return _randn(shape, g, 0.5 / math.sqrt(shape[1]))
+    if n.endswith("attn.fsmn_block.weight"):
+        return _randn(shape, g, 0.3 / math.sqrt(shape[2]))
+    if n == "quantizer._codebook.project_down.weight":
+        return _randn(shape, g, 0.6 / math.sqrt(shape[1]))
+    if n == "quantizer._codebook.project_down.bias":
+        return _randn(shape, g, 0.2)
     # ---- norms
     if "norm" in n or n.endswith("block.2.weight") or n.endswith("block.2.bias") or ".out.1." in n \
             or "layernorm" in n:

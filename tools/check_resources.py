@@ -27,7 +27,8 @@ GATED = [
     "est_resnet_kernel<unsigned short, 32, 4, 8, 2, false>", "est_resnet_kernel<unsigned short, 32, 4, 8, 2, true>",   # split build, 8 waves (cin = 256)
     "est_resnet_kernel<unsigned short, 32, 2, 4, 2, true>", "est_resnet_kernel<unsigned short, 32, 4, 4, 2, true>",
     "skinny3_kernel", "decode_attn_kernel", "sample_step_kernel", "attn_flash_kernel", "attn_flash_x_kernel", "attn_relpos",
-    "dac_ru_kernel", "gemm_win_kernel", "logmel_kernel", "pool_rows_kernel",
+    "dac_ru_kernel", "gemm_win_kernel", "logmel_kernel", "pool_rows_kernel", "logmel_w_kernel", "logmel_w_finish", "s3_rope_fsmn_kernel",
+    "fsq_encode_kernel", "rownorm_kernel",
 ]
 
 
@@ -52,7 +53,8 @@ def report(path):
             cur[k.split(" ")[0] + ("_spill" if "Spill" in k else "")] = int(v)
     names = demangle([r["name"] for r in rows])
     for r, n in zip(rows, names):
-        r["name"] = re.sub(r"\(anonymous namespace\)::|^void ", "", n.split("(")[0] if "<" not in n else n[:n.rindex(">") + 1])
+        n = re.sub(r"\(anonymous namespace\)::|^void ", "", n)
+        r["name"] = n.split("(")[0] if "<" not in n else n[:n.rindex(">") + 1]
     return rows
 
 
