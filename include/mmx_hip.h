@@ -189,8 +189,9 @@ int mmx_attn_relpos_x(const float* q, int64_t ldq, int64_t q_bs, const float* k,
                       hipStream_t stream);
 /* mmx_attn_flash_xs: the split build's attention on operands the PRODUCER has already split (MmxEstNext, MMX_X2 with
  * vt_out): qk bf16 [B][T][ldqk >= 2048] = [hi Q | hi K | lo Q | lo K], vt bf16 [B][2][512][ldvt], out fp32 [B][T][ldo].
- * form: 0 = workgroup shape chosen per launch (fastest alone); 1 = the shape that leaves LDS and registers for a co-resident
- * workgroup of another stream (launches beside the LM decode loop); 2 / 3 = 256-query / 4-wave 64-query workgroups (measurements).
+ * form: 0 = the default workgroup shape (fastest alone: 64-query workgroups on a small grid, else 128-query ones); 1 = the shape that
+ * leaves LDS and registers for a co-resident workgroup of another stream (launches beside the LM decode loop) - the same launch as 0
+ * since P stays in registers; 2 / 3 = 256-query / 4-wave 64-query workgroups (measurements).  Every form holds 64 KB of LDS.
  * The forms agree to fp32 rounding (different query-tile heights accumulate the online softmax over the same key tiles).
  * mmx_attn_flash_x: the same contract on fp32 operands:
  * q / k / v / out fp32, V ROW-major (v[b][t][h*D + d], ldv elements per

@@ -7,9 +7,13 @@
 // Structure (as attn_flash_kernel, csrc/attention.hip): block = 4 waves x 16*MF queries, key tiles of 64, everything
 // computed transposed (S^T = K Q^T, O^T = V^T P^T) so a lane owns one query; K and V^T tiles double buffered in LDS with
 // register-staged prefetch two tiles ahead, one workgroup barrier per key tile; lazy-rescale online softmax.
-// LDS images are UNPADDED 128-byte rows (64 bf16) with the 16-byte chunk index XOR-ed with (row & 7): the ds_read_b128
-// fragment reads (16 rows x 2 adjacent chunks per 16-lane service group, MI355X_MICROARCH.md "LDS") then land on 16
-// distinct 16-byte bank slots, and the tile needs no pad columns (hi + lo planes of K, V^T and P: 96 KB at MF = 2).
+// P never leaves the registers: lane (query l16, g) ends the softmax holding p of keys nf*16 + 4g + r (nf, r = 0..3), which as they
+// stand are the B fragment of the P V product's k-step ks (nf = 2ks, 2ks + 1) with its 8 k-slots meaning keys 32 ks + 16 (j >> 2) +
+// 4g + (j & 3) instead of 32 ks + 8g + j.  The V^T image is STORED in that order (16-byte slot 4 ks + g of a row = keys 32 ks + 4g .. + 3
+// and 32 ks + 16 + 4g .. + 3), so its fragment stays one ds_read_b128 per lane; K and the S product keep the natural order.
+// LDS images are UNPADDED 128-byte rows (64 bf16) with the 16-byte slot index XOR-ed with (row & 7): the ds_read_b128
+// fragment reads (16 rows x 2 adjacent slots per 16-lane service group, MI355X_MICROARCH.md "LDS") then land on 16
+// distinct 16-byte bank slots, and the tile needs no pad columns (hi + lo planes of K and V^T, double buffered: 64 KB in every form).
 #include "common.h"
 #include "../../include/mmx_hip.h"
 #include <cstdlib>
@@ -54,8 +58,6 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
     char* Kl = Kh + 2 * TILE;
     char* Vh = Kl + 2 * TILE;                          // [2 bufs][TILE]   channels x keys (V^T)
     char* Vl = Vh + 2 * TILE;
-    char* Ph = Vl + 2 * TILE;                          // [4 waves][QW rows x 128 B]   queries x keys
-    char* Pl = Ph + NW * QW * 128;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, l16 = lane & 15;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -130,8 +132,6 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
         const int e = ((q_begin + qt * (NW * QW)) / chunk + 1) * chunk;
         if (e < vis_all) vis_all = e;
     }
-    char* Pwh = Ph + wave * QW * 128;
-    char* Pwl = Pl + wave * QW * 128;
 
     // tile loads: 1024 chunks of 4 floats per operand, 4 per thread.
     //   K: chunk id -> (key r = id >> 4, channels 4*(id & 15) ..): coalesced 256-byte rows
@@ -176,8 +176,13 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
                 const int off = buf * TILE + swz(r, c8);
                 *reinterpret_cast<float4*>(Kh + off) = kreg[2 * pi];
                 *reinterpret_cast<float4*>(Kl + off) = kreg[2 * pi + 1];
-                *reinterpret_cast<float4*>(Vh + off) = vreg[2 * pi];
-                *reinterpret_cast<float4*>(Vl + off) = vreg[2 * pi + 1];
+                // keys 8 c8 .. +3 and 8 c8 + 4 .. +7: the low / high half (c8 >> 1 & 1) of two neighbouring 16-byte slots
+                const int vo = buf * TILE + swz(r, (c8 & 4) + 2 * (c8 & 1)) + ((c8 >> 1) & 1) * 8;
+                const int vo1 = vo ^ 16;               // slot + 1 (the slot index is even, the swizzle a XOR)
+                *reinterpret_cast<float2*>(Vh + vo) = make_float2(vreg[2 * pi].x, vreg[2 * pi].y);
+                *reinterpret_cast<float2*>(Vh + vo1) = make_float2(vreg[2 * pi].z, vreg[2 * pi].w);
+                *reinterpret_cast<float2*>(Vl + vo) = make_float2(vreg[2 * pi + 1].x, vreg[2 * pi + 1].y);
+                *reinterpret_cast<float2*>(Vl + vo1) = make_float2(vreg[2 * pi + 1].z, vreg[2 * pi + 1].w);
             }
             return;
         }
@@ -204,7 +209,9 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
                 const unsigned h0 = pack_bf16x2(a0, b0), h1 = pack_bf16x2(a1, b1);
                 const unsigned l0 = pack_bf16x2(a0 - __uint_as_float(h0 << 16), b0 - __uint_as_float(h0 & 0xffff0000u));
                 const unsigned l1 = pack_bf16x2(a1 - __uint_as_float(h1 << 16), b1 - __uint_as_float(h1 & 0xffff0000u));
-                const int o0 = buf * TILE + swz(d0, kp >> 2) + (kp & 3) * 4, o1 = buf * TILE + swz(d0 + 1, kp >> 2) + (kp & 3) * 4;
+                // keys 2kp, 2kp + 1 = 32 ks + 16 hf + 4 gk + (0 | 2), + 1: slot 4 ks + gk, half hf, dword kp & 1
+                const int vs = 4 * (kp >> 4) + ((kp >> 1) & 3), vb = ((kp >> 3) & 1) * 8 + (kp & 1) * 4;
+                const int o0 = buf * TILE + swz(d0, vs) + vb, o1 = buf * TILE + swz(d0 + 1, vs) + vb;
                 *reinterpret_cast<unsigned*>(Vh + o0) = h0;
                 *reinterpret_cast<unsigned*>(Vl + o0) = l0;
                 *reinterpret_cast<unsigned*>(Vh + o1) = h1;
@@ -239,33 +246,25 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
                 }
             }
         }
-        const bool need_mask = km || (j0 + KT > vis_all);
-        bool kvis[4][4];
-        if (need_mask) {
+        if (km || (j0 + KT > vis_all)) {               // a tile with masked pairs (the last ones of a row, or a key mask)
 #pragma unroll
             for (int nf = 0; nf < 4; ++nf)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int j = j0 + nf * 16 + 4 * g + r;
-                    kvis[nf][r] = j < Tk && (!km || km[j] != 0.f);
+                    const bool kvis = j < Tk && (!km || km[j] != 0.f);
+#pragma unroll
+                    for (int mf = 0; mf < MF; ++mf) s[mf][nf][r] = (j < lim[mf] && kvis) ? s[mf][nf][r] : -INFINITY;
                 }
         }
-        auto softmax_tile = [&](auto mask_c, auto mf_c) {
-            constexpr bool MASK = decltype(mask_c)::value;
+        uint2 ph[MF][4], pl[MF][4];                    // P of keys nf*16 + 4g .. +3, packed bf16 hi / lo
+        auto softmax_tile = [&](auto mf_c) {
             constexpr int mf = decltype(mf_c)::value;
             float mx = -INFINITY;
 #pragma unroll
             for (int nf = 0; nf < 4; ++nf)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float x = s[mf][nf][r];
-                    if constexpr (MASK) {
-                        const int j = j0 + nf * 16 + 4 * g + r;
-                        x = (j < lim[mf] && kvis[nf][r]) ? x : -INFINITY;
-                        s[mf][nf][r] = x;
-                    }
-                    mx = fmaxf(mx, x);
-                }
+                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[mf][nf][r]);
             mx *= sc2;
             float m_use = m_run[mf];
             const bool grow = (mx - m_run[mf]) > 6.0f || m_run[mf] == -INFINITY;     // lazy rescale (see attention.hip)
@@ -290,38 +289,26 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
 #pragma unroll
                 for (int r = 0; r < 4; ++r) p[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[mf][nf][r], sc2, -m_use));
                 rs += (p[0] + p[1]) + (p[2] + p[3]);
-                uint2 hi, lo;
-                split4(p, hi, lo);
-                // keys nf*16 + 4g .. +3 of query row mf*16 + l16: half a chunk
-                const int off = swz(mf * 16 + l16, nf * 2 + (g >> 1)) + (g & 1) * 8;
-                *reinterpret_cast<uint2*>(Pwh + off) = hi;
-                *reinterpret_cast<uint2*>(Pwl + off) = lo;
+                split4(p, ph[mf][nf], pl[mf][nf]);
             }
             l_run[mf] += rs;
         };
-        if (need_mask) {
-            softmax_tile(std::true_type{}, std::integral_constant<int, 0>{});
-            if constexpr (MF > 1) softmax_tile(std::true_type{}, std::integral_constant<int, MF - 1>{});
-        } else {
-            softmax_tile(std::false_type{}, std::integral_constant<int, 0>{});
-            if constexpr (MF > 1) softmax_tile(std::false_type{}, std::integral_constant<int, MF - 1>{});
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        short8_t aph[MF][2], apl[MF][2];               // lane (q = l16, g): P[q][ks*32 + 8g .. +7]
+        softmax_tile(std::integral_constant<int, 0>{});
+        if constexpr (MF > 1) softmax_tile(std::integral_constant<int, MF - 1>{});
+        // The S^T accumulators are the P operand as they stand: k-slot (g, j) of k-step ks is key 32 ks + 16 (j >> 2) + 4g + (j & 3)
+        short8_t aph[MF][2], apl[MF][2];
 #pragma unroll
         for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const int off = swz(mf * 16 + l16, ks * 4 + g);
-                aph[mf][ks] = *reinterpret_cast<const short8_t*>(Pwh + off);
-                apl[mf][ks] = *reinterpret_cast<const short8_t*>(Pwl + off);
+                aph[mf][ks] = __builtin_bit_cast(short8_t, make_uint4(ph[mf][2 * ks].x, ph[mf][2 * ks].y, ph[mf][2 * ks + 1].x, ph[mf][2 * ks + 1].y));
+                apl[mf][ks] = __builtin_bit_cast(short8_t, make_uint4(pl[mf][2 * ks].x, pl[mf][2 * ks].y, pl[mf][2 * ks + 1].x, pl[mf][2 * ks + 1].y));
             }
 #pragma unroll
         for (int df = 0; df < 4; ++df)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const int off = buf * TILE + swz(df * 16 + l16, ks * 4 + g);
+                const int off = buf * TILE + swz(df * 16 + l16, ks * 4 + g);      // the slot holds this lane's 8 keys in P's order
                 const short8_t bvh = *reinterpret_cast<const short8_t*>(Vh + off);
                 const short8_t bvl = *reinterpret_cast<const short8_t*>(Vl + off);
 #pragma unroll
@@ -331,7 +318,6 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
                     o[mf][df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bvl, aph[mf][ks], o[mf][df], 0, 0, 0);
                 }
             }
-        __builtin_amdgcn_wave_barrier();
     }
 #pragma unroll
     for (int mf = 0; mf < MF; ++mf) {
@@ -640,7 +626,7 @@ template <int MF, bool PRE, int NW>
 int launch_flash_x(dim3 grid, hipStream_t stream, const void* q, long ldq, long q_bs, const void* k, long ldk, long k_bs,
                    const void* v, long ldv, long v_bs, float* out, long ldo, long o_bs, int T_, float scale,
                    const float* keymask, long km_bs, int chunk, int nq, int H, int npairs, int q_begin, const int32_t* klen) {
-    const size_t lds = (size_t)8 * 64 * 128 + (size_t)2 * NW * 16 * MF * 128;
+    const size_t lds = (size_t)8 * 64 * 128;           // K and V^T, hi + lo planes, double buffered
     MMX_LDS_OPT_IN((attn_flash_x_kernel<MF, PRE, NW>), lds);
     hipLaunchKernelGGL((attn_flash_x_kernel<MF, PRE, NW>), grid, dim3(64 * NW), lds, stream, q, ldq, q_bs, k, ldk, k_bs, v, ldv, v_bs, out, ldo, o_bs, T_,
                        scale, keymask, km_bs, chunk, nq, H, npairs, q_begin, klen);
@@ -680,23 +666,21 @@ extern "C" int mmx_attn_flash_xs(const void* qk, int64_t ldqk, int64_t qk_bs, co
     const int qtile = small ? 64 : 128, nq = (Tq + qtile - 1) / qtile;
     dim3 grid(8 * ((npairs + 7) / 8) * nq);
     const bf16_t* q = (const bf16_t*)qk;
-    // 8 waves x 32 queries (256 per workgroup, MF = 2) halve the K / V fragment reads from LDS per MFMA, and a workgroup takes
-    // ~1.6 x as long as one of 128 queries (tools/flash_lab.py, profiles/r04_flash_lab_x.txt: 71 -> 62 us at 3 x 980 frames,
-    // 37 -> 30 at 5 x 420, 122 -> 112 at 8 x 896; 93 -> 100 at 5 x 860, where the 128-query grid needs 3 rounds of the 256 CUs
-    // and the 256-query grid 2).  form 0: chosen per launch from the rounds each grid needs.
-    // form 1 (the caller's launch runs BESIDE a latency-bound kernel chain on another stream): the 128-query workgroups - 96 KB of
-    // LDS and 136 registers per wave (two waves per SIMD leave 224) instead of 128 KB and 216 (80): a decode workgroup of csrc/decode.hip
-    // fits on the same CU.  Measured in the 32-utterance step (gpurun_out/r4_17): decode loop done at 524 ms against 541 (chosen
-    // per launch) and 549 (256-query everywhere); 520.8 / 512.4 / 510.7 audio-s/s.  form 2: 256-query workgroups wherever the
-    // grid is not small; form 3: the 4-wave 64-query form everywhere (80 KB of LDS).
+    // Every form holds 64 KB of LDS (K and V^T, hi + lo, double buffered); P stays in registers.  The 128-query workgroups
+    // (<1, true, 8>, 114 registers per wave) are the form of every grid that is not small: two of them fit on a CU, and alone on
+    // the chip they beat the 256-query form (<2, true, 8>: 8 waves x 32 queries, half the K / V fragment reads per MFMA, 168
+    // registers) on every shape tools/flash_lab.py sweeps - 56.6 against 57.6 us at 3 x 980 frames, 27.6 / 28.4 at 5 x 420,
+    // 74 / 94 at 5 x 860, 24.0 / 25.6 at 6 x 330, 96 / 106 at 8 x 896 (profiles/r05_flash_lab_x.txt; with P in LDS it was the
+    // other way round on four of the five, and form 0 chose by the rounds each grid needs).  form 0 and form 1 are therefore the
+    // same launch.  form 1 stays the name of the shape for launches BESIDE a latency-bound kernel chain on another stream: two of
+    // its waves leave more than half of a SIMD's registers, so a decode workgroup of csrc/decode.hip fits on the same CU.
+    // form 2: 256-query workgroups wherever the grid is not small; form 3: the 4-wave 64-query form everywhere.
     const int nq2 = (Tq + 255) / 256;
-    const long wg1 = (long)npairs * nq, wg2 = (long)npairs * nq2;
-    const bool mf2 = !small && form != 1 && (form == 2 || 1.6 * (double)((wg2 + 255) / 256) < (double)((wg1 + 255) / 256));
-    if (mf2) {
+    if (!small && form == 2) {
         dim3 grid2(8 * ((npairs + 7) / 8) * nq2);
         return launch_flash_x<2, true, 8>(grid2, stream, q, ldqk, qk_bs, q + 512, ldqk, qk_bs, vt, ldvt, vt_bs, out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq2, H, npairs, q_begin, klen);
     }
-    // (4 waves x 32 queries - the 256-query form's fragment reuse on 96 KB of LDS, one wave per SIMD - measured 118 us at 5 x 860
+    // (4 waves x 32 queries - the 256-query form's fragment reuse with one wave per SIMD - measured 118 us at 5 x 860
     // frames against 92: one wave per SIMD has nothing to overlap its softmax with)
     if (small) return launch_flash_x<1, true, 4>(grid, stream, q, ldqk, qk_bs, q + 512, ldqk, qk_bs, vt, ldvt, vt_bs, out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq, H, npairs, q_begin, klen);
     return launch_flash_x<1, true, 8>(grid, stream, q, ldqk, qk_bs, q + 512, ldqk, qk_bs, vt, ldvt, vt_bs, out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq, H, npairs, q_begin, klen);

@@ -162,9 +162,9 @@ class FlowEngine:
         # beside them on another stream (the LM decode loop of TtsEngine.tts_batch) keeps more of the chip
         # (measured, 32-utterance step: decode loop 548 -> 523 ms, step 643 -> 622 ms).  Part of the plan key.
         self.polite = False
-        # polite groups of the split build: flash attention on its 128-query workgroups (96 KB of LDS, 136 registers per wave) instead
-        # of the 256-query ones (128 KB, 216) the launch-time rule would pick: a decode workgroup fits beside them on the CU
-        # (measured in the step: decode loop done at 524 ms against 541, 520.8 against 512.4 audio-s/s; include/mmx_hip.h, form)
+        # polite groups of the split build: flash attention on its 128-query workgroups (64 KB of LDS, 114 registers per wave), the
+        # form a decode workgroup fits beside on the CU (include/mmx_hip.h, form).  Since the kernel keeps P in registers this is
+        # also what form 0 launches on every grid that is not small; the switch stays for measurements.
         self.polite_flash_form = getattr(FlowEngine, "polite_flash_form_default", 1)
         self.plan_bytes = 0
         # CausalConditionalCFM.__init__: torch CPU manual_seed(0); randn([1,80,15000]) (flow_matching.py:320-321)

@@ -32,6 +32,15 @@ GATED = [
 ]
 
 
+# register ceilings (VGPRs + AGPRs per wave) that a design decision rests on, and the dynamic LDS the launcher asks for (bytes; the
+# compiler does not see it: read from the launcher's source)
+#   attn_flash_x_kernel<1, true, 8>: the form launched beside the LM decode loop.  Two of its waves per SIMD must leave 224 registers
+#   for decode workgroups (2 x 96-112): (512 - 224) / 2 = 144.  Every form of the kernel holds 64 KB of LDS (K and V^T, hi + lo planes,
+#   double buffered; P stays in registers), so two 128-query workgroups, or one and a decode workgroup, fit in a CU's 160 KB.
+REG_MAX = {"attn_flash_x_kernel<1, true, 8>": 144}
+LDS_EXPECT = {"attention_x.hip": ("launch_flash_x", r"const size_t lds = \(size_t\)8 \* 64 \* 128;", 64 * 1024)}
+
+
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout
     return out.strip().split("\n")
@@ -61,7 +70,7 @@ def report(path):
 def main():
     files = [a for a in sys.argv[1:] if a.endswith(".hip")] or sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     show_all = "--all" in sys.argv
-    bad = []
+    bad, over = [], []
     for f in files:
         for r in report(os.path.join(CSRC, f)):
             gated = any(g in r["name"] for g in GATED)
@@ -71,10 +80,21 @@ def main():
                       f"occ {r.get('Occupancy', 0)}{'  GATED' if gated else ''}{'  SPILLS' if spills else ''}")
             if gated and spills:
                 bad.append(r["name"])
+            cap = REG_MAX.get(r["name"])
+            if cap is not None and r.get("VGPRs", 0) + r.get("AGPRs", 0) > cap:
+                over.append(f"{r['name']}: {r.get('VGPRs', 0) + r.get('AGPRs', 0)} registers > {cap}")
+        if f in LDS_EXPECT:
+            fn, pat, nbytes = LDS_EXPECT[f]
+            src = open(os.path.join(CSRC, f)).read()
+            if not re.search(pat, src[src.index(fn):]):
+                over.append(f"{f}: {fn} no longer asks for {nbytes} bytes of LDS")
     if bad:
         print("\nspilling kernels on a default path:\n  " + "\n  ".join(bad))
         sys.exit(1)
-    print("\nno gated default-path kernel spills")
+    if over:
+        print("\nresource expectations not met:\n  " + "\n  ".join(over))
+        sys.exit(1)
+    print("\nno gated default-path kernel spills; register ceilings and LDS sizes as expected")
 
 
 if __name__ == "__main__":
