@@ -3,7 +3,7 @@
 //                       masks) — the parity path and the conformer encoder (10 layers, once per utterance).
 //   attn_flash_kernel : bf16 MFMA flash attention for the estimator's 56 blocks x 10 Euler steps
 //                       (the flow's dominant FLOPs: SURVEY.md §8d, 57.3 of 189.5 GFLOP per call).
-#include "common.h"
+#include "attn_tile.h"
 #include "../../include/mmx_hip.h"
 #include <type_traits>
 #include <utility>
@@ -184,27 +184,21 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(
     __shared__ __attribute__((aligned(16))) bf16_t Ps[NW][QW * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, l16 = lane & 15;
-    // XCD-aware mapping (1-D grid): the query tiles of one (batch, head) pair read the same K / V^T rows; they get
-    // linear ids with the same id % 8, i.e. the same XCD and L2, instead of being dealt round robin over all eight.
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int pair = (slot / nq) * 8 + xcd;
-    if (pair >= npairs) return;                        // uniform: the grid is padded to a multiple of 8 pairs
-    const int qt = slot % nq;
-    const int b = pair / nheads, h = pair % nheads;
-    const int qb = q_begin + qt * (NW * QW) + wave * QW;   // this wave's first query
+    const PairTile pt = pair_tile(nq, nheads, npairs);
+    if (!pt.valid) return;
+    const int b = pt.b, h = pt.h;
+    const int q0 = q_begin + pt.qt * (NW * QW), qb = q0 + wave * QW;   // the workgroup's, this wave's first query
     q += (long)b * q_bs + h * D;
     k += (long)b * k_bs + h * D;
     vt += (long)b * vt_bs + (long)h * D * ldvt;
     out += (long)b * o_bs + h * D;
     const float* km = keymask ? keymask + (long)b * km_bs : nullptr;
     const float sc2 = scale * 1.44269504088896341f;    // scores in log2 units
-    // klen: the batch row's number of valid keys (a padded batch whose masks are prefixes).  Unlike a key mask it is known
-    // before the loop: key tiles beyond it are never visited, tiles inside it run the unmasked code, only the boundary
-    // tile compares; a workgroup whose queries are all padding writes zeros and leaves.
-    const int Tk = klen ? (klen[b] < Tn ? klen[b] : Tn) : Tn;
-    if (klen && q_begin + qt * (NW * QW) >= Tk) {        // uniform per workgroup, before any barrier
+    // a workgroup whose queries are all padding (beyond klen[b]) writes zeros and leaves
+    const auto [Tk, kend, ntile, vis_all] = key_window(Tn, klen, b, chunk, q0, NW * QW);
+    if (klen && q0 >= Tk) {                            // uniform per workgroup, before any barrier
         for (int id = tid; id < NW * QW * 8; id += 64 * NW) {
-            const int i = q_begin + qt * (NW * QW) + (id >> 3);
+            const int i = q0 + (id >> 3);
             if (i < Tn) *reinterpret_cast<uint4*>(out + (long)i * ldo + (id & 7) * 8) = make_uint4(0, 0, 0, 0);
         }
         return;
@@ -238,26 +232,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(
         for (int i = 0; i < 4; ++i) o[mf][i] = float4_t{0.f, 0.f, 0.f, 0.f};
         m_run[mf] = -INFINITY;
         l_run[mf] = 0.f;
-        const int i = qb + mf * 16 + l16;
-        int e = Tk;
-        if (chunk > 0) { int c2 = (i / chunk + 1) * chunk; e = c2 < e ? c2 : e; }
-        lim[mf] = e;
-    }
-    // keys beyond the last query's chunk are invisible to the whole block
-    int kend = Tk;
-    if (chunk > 0) {
-        int qlast = q_begin + qt * (NW * QW) + NW * QW - 1;
-        if (qlast > Tn - 1) qlast = Tn - 1;
-        int e = (qlast / chunk + 1) * chunk;
-        if (e < kend) kend = e;
-    }
-    const int ntile = (kend + KT - 1) / KT;
-    // keys below vis_all are visible to EVERY query of the workgroup (its first query's chunk end): those tiles run the
-    // unmasked code; only the tiles that reach into the block's own chunks compare
-    int vis_all = Tk;
-    if (chunk > 0) {
-        const int e = ((q_begin + qt * (NW * QW)) / chunk + 1) * chunk;
-        if (e < vis_all) vis_all = e;
+        lim[mf] = lane_limit(qb + mf * 16 + l16, chunk, Tk);
     }
     bf16_t* Pw = Ps[wave];
 
@@ -347,12 +322,8 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(
                     mx = fmaxf(mx, x);
                 }
             mx *= sc2;                                 // this LANE's maximum: keys 4g + r of the tile's four 16-key fragments
-            // lazy rescale (cdna_hip_programming.md T13): keep the old running max while every score of the wave is at
-            // most 2^6 above it; p then reaches at most 64 (fine in bf16 / fp32 sums) and the O accumulators (AGPRs: a
-            // rescale costs a read + multiply + write per value) are left alone.  The test needs no cross-lane maximum
-            // (each lane checks its own keys against the query's running max, one wave vote), so a steady-state tile has
-            // no shuffle at all (ds_bpermute round trips sat on the critical path of a one-wave-per-SIMD loop); the four
-            // lanes of a query agree on the maximum only when it moves.  m_run stays uniform over those four lanes.
+            // the text of lazy_rescale (attn_tile.h), kept here: through the helper the compiler multiplies o as whole vectors and
+            // <2, true, 4> comes out at 154 VGPRs + 80 AGPRs instead of 158 + 72
             float m_use = m_run[mf];
             const bool grow = (mx - m_run[mf]) > 6.0f || m_run[mf] == -INFINITY;
             if (__any(grow)) {
@@ -442,10 +413,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(
         __builtin_amdgcn_wave_barrier();               // the patch is rewritten in the next tile
     }
 #pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {                  // (all lanes: the shuffles come before the row guard)
-        l_run[mf] += __shfl_xor(l_run[mf], 16, 64);
-        l_run[mf] += __shfl_xor(l_run[mf], 32, 64);
-    }
+    for (int mf = 0; mf < MF; ++mf) row_sum(l_run[mf]);
 #pragma unroll
     for (int mf = 0; mf < MF; ++mf) {
         const int i = qb + mf * 16 + l16;
@@ -483,12 +451,10 @@ __global__ __launch_bounds__(64 * NW) void attn_relpos_kernel(
     __shared__ __attribute__((aligned(16))) float Bp[NW][16 * BW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, l16 = lane & 15;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int pair = (slot / nq) * 8 + xcd;
-    if (pair >= npairs) return;
-    const int qt = slot % nq;
-    const int b = pair / nheads, h = pair % nheads;
-    const int qb = qt * (NW * 16) + wave * 16;
+    const PairTile pt = pair_tile(nq, nheads, npairs);
+    if (!pt.valid) return;
+    const int b = pt.b, h = pt.h;
+    const int q0 = pt.qt * (NW * 16), qb = q0 + wave * 16;
     q += (long)b * q_bs + h * D;
     k += (long)b * k_bs + h * D;
     vt += (long)b * vt_bs + (long)h * D * ldvt;
@@ -524,11 +490,10 @@ __global__ __launch_bounds__(64 * NW) void attn_relpos_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) o[i] = float4_t{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
-    int lim = Tk;
-    if (chunk > 0) { const int c2 = ((qb + l16) / chunk + 1) * chunk; lim = c2 < lim ? c2 : lim; }
-    int kend = Tk;
+    const int lim = lane_limit(qb + l16, chunk, Tk);
+    int kend = Tk;                                     // key_window's text, kept: through the helper this kernel takes 162 VGPRs, not 176
     if (chunk > 0) {
-        int qlast = qt * (NW * 16) + NW * 16 - 1;
+        int qlast = q0 + NW * 16 - 1;
         if (qlast > Tn - 1) qlast = Tn - 1;
         const int e = (qlast / chunk + 1) * chunk;
         if (e < kend) kend = e;
@@ -536,7 +501,7 @@ __global__ __launch_bounds__(64 * NW) void attn_relpos_kernel(
     const int ntile = (kend + KT - 1) / KT;
     int vis_all = Tk;
     if (chunk > 0) {
-        const int e = ((qt * (NW * 16)) / chunk + 1) * chunk;
+        const int e = (q0 / chunk + 1) * chunk;
         if (e < vis_all) vis_all = e;
     }
     float* Bw = Bp[wave];
@@ -632,23 +597,7 @@ __global__ __launch_bounds__(64 * NW) void attn_relpos_kernel(
                 }
                 mx = fmaxf(mx, x);
             }
-        mx *= sc2;
-        float m_use = m_run;
-        const bool grow = (mx - m_run) > 6.0f || m_run == -INFINITY;
-        if (__any(grow)) {
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);
-            const float m_safe = m_new == -INFINITY ? 0.f : m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_safe);
-            l_run *= alpha;
-#pragma unroll
-            for (int df = 0; df < 4; ++df)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[df][r] *= alpha;
-            m_run = m_new;
-            m_use = m_safe;
-        }
+        const float m_use = lazy_rescale(mx * sc2, m_run, l_run, o);
         float rs = 0.f;
 #pragma unroll
         for (int nf = 0; nf < 4; ++nf) {
@@ -678,8 +627,7 @@ __global__ __launch_bounds__(64 * NW) void attn_relpos_kernel(
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();               // the patch is rewritten in the next tile
     }
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
+    row_sum(l_run);
     const int i = qb + l16;
     if (i < Tn) {
         const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
@@ -702,7 +650,7 @@ extern "C" int mmx_attn_relpos_bf16(const void* q, int64_t ldq, int64_t q_bs, co
     MMX_CHECK_ARG(ldvt >= ((T_ + 7) / 8) * 8 && ldo % 4 == 0 && o_bs % 4 == 0);
     MMX_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)pos % 16) == 0 && ((uintptr_t)out % 8) == 0);
     const int npairs = H * B, nq = (T_ + 63) / 64;
-    hipLaunchKernelGGL((attn_relpos_kernel<4>), dim3(8 * ((npairs + 7) / 8) * nq), dim3(256), 0, stream, (const bf16_t*)q, ldq, q_bs,
+    hipLaunchKernelGGL((attn_relpos_kernel<4>), pair_grid(npairs, nq), dim3(256), 0, stream, (const bf16_t*)q, ldq, q_bs,
                        (const bf16_t*)k, ldk, k_bs, (const bf16_t*)vt, ldvt, vt_bs, (const bf16_t*)pos, ldp, pos_u, pos_v, (bf16_t*)out, ldo,
                        o_bs, T_, scale, chunk, nq, H, npairs, klen);
     MMX_LAUNCH_CHECK();
@@ -729,12 +677,10 @@ __global__ __launch_bounds__(256) void attn_flash_splitk_kernel(
     bf16_t* Kw = reinterpret_cast<bf16_t*>(smem_raw) + wave * (2 * KT * LDK + 16 * LD);   // this wave's K tile
     bf16_t* Vw = Kw + KT * LDK;                                                         // ... V^T tile
     bf16_t* Pw = Vw + D * LDK;                                                          // ... P patch
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int pair = (slot / nq) * 8 + xcd;
-    if (pair >= npairs) return;
-    const int qt = slot % nq;
-    const int b = pair / nheads, h = pair % nheads;
-    const int qb = q_begin + qt * 16;                  // the workgroup's 16 queries
+    const PairTile pt = pair_tile(nq, nheads, npairs);
+    if (!pt.valid) return;
+    const int b = pt.b, h = pt.h;
+    const int qb = q_begin + pt.qt * 16;               // the workgroup's 16 queries
     q += (long)b * q_bs + h * D;
     k += (long)b * k_bs + h * D;
     vt += (long)b * vt_bs + (long)h * D * ldvt;
@@ -754,24 +700,9 @@ __global__ __launch_bounds__(256) void attn_flash_splitk_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) o[i] = float4_t{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
-    int lim = Tn;
-    {
-        const int i = qb + l16;
-        if (chunk > 0) { int c2 = (i / chunk + 1) * chunk; lim = c2 < lim ? c2 : lim; }
-    }
-    int kend = Tn;
-    if (chunk > 0) {
-        int qlast = qb + 15;
-        if (qlast > Tn - 1) qlast = Tn - 1;
-        int e = (qlast / chunk + 1) * chunk;
-        if (e < kend) kend = e;
-    }
-    const int ntile = (kend + KT - 1) / KT;
-    int vis_all = Tn;                                  // keys below it are visible to all 16 queries: unmasked tiles
-    if (chunk > 0) {
-        const int e = (qb / chunk + 1) * chunk;
-        if (e < vis_all) vis_all = e;
-    }
+    const int lim = lane_limit(qb + l16, chunk, Tn);
+    const KeyWindow kw = key_window(Tn, nullptr, b, chunk, qb, 16);     // no klen here: Tk = Tn
+    const int ntile = kw.ntile, vis_all = kw.vis_all;
 
     uint4 kreg[8], vreg[8];
     auto load_tiles = [&](int j0) {
@@ -826,24 +757,7 @@ __global__ __launch_bounds__(256) void attn_flash_splitk_kernel(
                 }
                 mx = fmaxf(mx, x);
             }
-        mx *= sc2;
-        // as in attn_flash_kernel: the running max moves (with one cross-lane maximum) only when some score of the wave
-        // is more than 2^6 above it; a steady-state tile has no shuffle
-        float m_safe = m_run;
-        const bool grow = (mx - m_run) > 6.0f || m_run == -INFINITY;
-        if (__any(grow)) {
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);
-            m_safe = m_new == -INFINITY ? 0.f : m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_safe);
-            l_run *= alpha;
-#pragma unroll
-            for (int df = 0; df < 4; ++df)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[df][r] *= alpha;
-            m_run = m_new;
-        }
+        const float m_safe = lazy_rescale(mx * sc2, m_run, l_run, o);
         float rs = 0.f;
 #pragma unroll
         for (int nf = 0; nf < 4; ++nf) {
@@ -879,8 +793,7 @@ __global__ __launch_bounds__(256) void attn_flash_splitk_kernel(
     for (int df = 0; df < 4; ++df)
 #pragma unroll
         for (int r = 0; r < 4; ++r) part[(wave * 16 + l16) * 65 + df * 16 + 4 * g + r] = o[df][r];
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
+    row_sum(l_run);
     if (g == 0) { pm[wave * 16 + l16] = m_run; pl[wave * 16 + l16] = l_run; }
     __syncthreads();
     {
@@ -909,60 +822,47 @@ __global__ __launch_bounds__(256) void attn_flash_splitk_kernel(
     }
 }
 
-extern "C" int mmx_attn_flash_bf16(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64_t ldk, int64_t k_bs,
-                                   const void* vt, int64_t ldvt, int64_t vt_bs, void* out, int64_t ldo, int64_t o_bs,
-                                   int B, int H, int T_, float scale, const float* keymask, int64_t km_bs, int chunk,
-                                   int q_begin, const int32_t* klen, hipStream_t stream) {
-    MMX_CHECK_ARG(q && k && vt && out && B > 0 && H > 0 && T_ > 0 && chunk >= 0);
-    MMX_CHECK_ARG(q_begin >= 0 && q_begin < T_ && q_begin % 16 == 0);
-    MMX_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 && vt_bs % 8 == 0);
-    MMX_CHECK_ARG(ldvt >= ((T_ + 7) / 8) * 8);
-    MMX_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)vt % 16) == 0);
-    const int npairs = H * B;
-    const int Tq = T_ - q_begin;
-    if ((long)npairs * ((Tq + 63) / 64) < 96 && T_ >= 512 && !klen) {            // few queries, many keys: split the keys over waves
-        const int nq16 = (Tq + 15) / 16;
-        const size_t lds = 4 * (2 * 64 * 80 + 16 * 72) * sizeof(bf16_t);   // >= the merge buffers (4*16*65 + 128 floats)
-        MMX_LDS_OPT_IN(attn_flash_splitk_kernel, lds);
-        hipLaunchKernelGGL(attn_flash_splitk_kernel, dim3(8 * ((npairs + 7) / 8) * nq16), dim3(256), lds, stream, (const bf16_t*)q, ldq,
-                           q_bs, (const bf16_t*)k, ldk, k_bs, (const bf16_t*)vt, ldvt, vt_bs, (bf16_t*)out, ldo, o_bs, T_, scale, keymask,
-                           km_bs, chunk, nq16, H, npairs, q_begin);
-        MMX_LAUNCH_CHECK();
-        return MMX_OK;
-    }
-    const bool small = (long)npairs * ((Tq + 127) / 128) < 192;         // fewer 128-query tiles than ~3/4 of the CUs
-    const int qtile = small ? 64 : 128, nq = (Tq + qtile - 1) / qtile;
-    dim3 grid(8 * ((npairs + 7) / 8) * nq);
-    if (small)
-        hipLaunchKernelGGL((attn_flash_kernel<1, false>), grid, dim3(256), 0, stream, (const bf16_t*)q, ldq, q_bs, (const bf16_t*)k, ldk, k_bs,
-                           (const bf16_t*)vt, ldvt, vt_bs, (bf16_t*)out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq, H, npairs, q_begin, klen);
-    else
-        hipLaunchKernelGGL((attn_flash_kernel<1, false, 8>), grid, dim3(512), 0, stream, (const bf16_t*)q, ldq, q_bs, (const bf16_t*)k, ldk, k_bs,
-                           (const bf16_t*)vt, ldvt, vt_bs, (bf16_t*)out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq, H, npairs, q_begin, klen);
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
-}
-
-
-extern "C" int mmx_attn_flash_fp8(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64_t ldk, int64_t k_bs,
-                                  const void* vt, int64_t ldvt, int64_t vt_bs, void* out, int64_t ldo, int64_t o_bs,
-                                  int B, int H, int T_, float scale, const float* keymask, int64_t km_bs, int chunk,
-                                  int q_begin, const int32_t* klen, hipStream_t stream) {
+// mmx_attn_flash_bf16 / mmx_attn_flash_fp8: one set of argument checks and tile rules, the kernels differ in FP8
+template <bool FP8>
+static int launch_flash(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64_t ldk, int64_t k_bs, const void* vt, int64_t ldvt,
+                        int64_t vt_bs, void* out, int64_t ldo, int64_t o_bs, int B, int H, int T_, float scale, const float* keymask,
+                        int64_t km_bs, int chunk, int q_begin, const int32_t* klen, hipStream_t stream) {
     MMX_CHECK_ARG(q && k && vt && out && B > 0 && H > 0 && T_ > 0 && chunk >= 0);
     MMX_CHECK_ARG(q_begin >= 0 && q_begin < T_ && q_begin % 16 == 0);
     MMX_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 && vt_bs % 8 == 0);
     MMX_CHECK_ARG(ldvt >= ((T_ + 7) / 8) * 8);
     MMX_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)vt % 16) == 0);
     const int npairs = H * B, Tq = T_ - q_begin;
-    const bool small = (long)npairs * ((Tq + 127) / 128) < 192;
-    const int qtile = small ? 64 : 128, nq = (Tq + qtile - 1) / qtile;
-    dim3 grid(8 * ((npairs + 7) / 8) * nq);
-    if (small)
-        hipLaunchKernelGGL((attn_flash_kernel<1, true>), grid, dim3(256), 0, stream, (const bf16_t*)q, ldq, q_bs, (const bf16_t*)k, ldk, k_bs,
-                           (const bf16_t*)vt, ldvt, vt_bs, (bf16_t*)out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq, H, npairs, q_begin, klen);
-    else
-        hipLaunchKernelGGL((attn_flash_kernel<2, true>), grid, dim3(256), 0, stream, (const bf16_t*)q, ldq, q_bs, (const bf16_t*)k, ldk, k_bs,
-                           (const bf16_t*)vt, ldvt, vt_bs, (bf16_t*)out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq, H, npairs, q_begin, klen);
+    auto launch = [&](auto kernel, dim3 grid, int threads, size_t lds, int nq, auto... tail) {
+        hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, stream, (const bf16_t*)q, ldq, q_bs, (const bf16_t*)k, ldk, k_bs, (const bf16_t*)vt,
+                           ldvt, vt_bs, (bf16_t*)out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq, H, npairs, q_begin, tail...);
+    };
+    if (!FP8 && (long)npairs * ((Tq + 63) / 64) < 96 && T_ >= 512 && !klen) {     // few queries, many keys: split the keys over waves
+        const int nq16 = (Tq + 15) / 16;
+        const size_t lds = 4 * (2 * 64 * 80 + 16 * 72) * sizeof(bf16_t);   // >= the merge buffers (4*16*65 + 128 floats)
+        MMX_LDS_OPT_IN(attn_flash_splitk_kernel, lds);
+        launch(attn_flash_splitk_kernel, pair_grid(npairs, nq16), 256, lds, nq16);
+    } else {
+        const bool small = few_tiles(npairs, Tq);
+        const int qtile = small ? 64 : 128, nq = (Tq + qtile - 1) / qtile;
+        if (small) launch(attn_flash_kernel<1, FP8>, pair_grid(npairs, nq), 256, 0, nq, klen);
+        else if (FP8) launch(attn_flash_kernel<2, true>, pair_grid(npairs, nq), 256, 0, nq, klen);
+        else launch(attn_flash_kernel<1, false, 8>, pair_grid(npairs, nq), 512, 0, nq, klen);
+    }
     MMX_LAUNCH_CHECK();
     return MMX_OK;
+}
+
+extern "C" int mmx_attn_flash_bf16(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64_t ldk, int64_t k_bs,
+                                   const void* vt, int64_t ldvt, int64_t vt_bs, void* out, int64_t ldo, int64_t o_bs,
+                                   int B, int H, int T_, float scale, const float* keymask, int64_t km_bs, int chunk,
+                                   int q_begin, const int32_t* klen, hipStream_t stream) {
+    return launch_flash<false>(q, ldq, q_bs, k, ldk, k_bs, vt, ldvt, vt_bs, out, ldo, o_bs, B, H, T_, scale, keymask, km_bs, chunk, q_begin, klen, stream);
+}
+
+extern "C" int mmx_attn_flash_fp8(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64_t ldk, int64_t k_bs,
+                                  const void* vt, int64_t ldvt, int64_t vt_bs, void* out, int64_t ldo, int64_t o_bs,
+                                  int B, int H, int T_, float scale, const float* keymask, int64_t km_bs, int chunk,
+                                  int q_begin, const int32_t* klen, hipStream_t stream) {
+    return launch_flash<true>(q, ldq, q_bs, k, ldk, k_bs, vt, ldvt, vt_bs, out, ldo, o_bs, B, H, T_, scale, keymask, km_bs, chunk, q_begin, klen, stream);
 }

@@ -4,9 +4,10 @@
 // lo x lo term (2^-18 relative) is dropped.  Same contract as mmx_attn_flash_bf16 except that V comes ROW-major
 // (v[b][t][h*D + d], the QKV projection's own output): the workgroup transposes its V tile on the way into LDS.
 //
-// Structure (as attn_flash_kernel, csrc/attention.hip): block = 4 waves x 16*MF queries, key tiles of 64, everything
+// Structure (the scheme of attn_flash_kernel, csrc/attention.hip): block = NW waves x 16*MF queries, key tiles of 64, everything
 // computed transposed (S^T = K Q^T, O^T = V^T P^T) so a lane owns one query; K and V^T tiles double buffered in LDS with
-// register-staged prefetch two tiles ahead, one workgroup barrier per key tile; lazy-rescale online softmax.
+// register-staged prefetch two tiles ahead, one workgroup barrier per key tile.  The workgroup mapping, the key window, the
+// lazy-rescale step of the online softmax and the row sum are the helpers of csrc/attn_tile.h, shared with attention.hip.
 // P never leaves the registers: lane (query l16, g) ends the softmax holding p of keys nf*16 + 4g + r (nf, r = 0..3), which as they
 // stand are the B fragment of the P V product's k-step ks (nf = 2ks, 2ks + 1) with its 8 k-slots meaning keys 32 ks + 16 (j >> 2) +
 // 4g + (j & 3) instead of 32 ks + 8g + j.  The V^T image is STORED in that order (16-byte slot 4 ks + g of a row = keys 32 ks + 4g .. + 3
@@ -14,7 +15,7 @@
 // LDS images are UNPADDED 128-byte rows (64 bf16) with the 16-byte slot index XOR-ed with (row & 7): the ds_read_b128
 // fragment reads (16 rows x 2 adjacent slots per 16-lane service group, MI355X_MICROARCH.md "LDS") then land on 16
 // distinct 16-byte bank slots, and the tile needs no pad columns (hi + lo planes of K and V^T, double buffered: 64 KB in every form).
-#include "common.h"
+#include "attn_tile.h"
 #include "../../include/mmx_hip.h"
 #include <cstdlib>
 #include <type_traits>
@@ -30,6 +31,58 @@ __device__ __forceinline__ void split4(const float x[4], uint2& hi, uint2& lo) {
     hi.y = pack_bf16x2(x[2], x[3]);
     lo.x = pack_bf16x2(x[0] - __uint_as_float(hi.x << 16), x[1] - __uint_as_float(hi.x & 0xffff0000u));
     lo.y = pack_bf16x2(x[2] - __uint_as_float(hi.y << 16), x[3] - __uint_as_float(hi.y & 0xffff0000u));
+}
+// 8 consecutive channels -> one MFMA operand fragment per plane
+__device__ __forceinline__ void split8(const float x[8], short8_t& hi, short8_t& lo) {
+    uint2 h0, l0, h1, l1;
+    split4(x, h0, l0);
+    split4(x + 4, h1, l1);
+    hi = __builtin_bit_cast(short8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
+    lo = __builtin_bit_cast(short8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));
+}
+__device__ __forceinline__ void split8(const float4& a, const float4& c, short8_t& hi, short8_t& lo) {
+    const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+    split8(x, hi, lo);
+}
+
+// fp32 K / V tiles of the kernels that split them themselves (attn_flash_x_kernel<.., PRE = false, ..>, attn_relpos_x_kernel):
+// 1024 chunks of 4 floats per operand over NT threads.
+//   K: chunk id -> (key r = id >> 4, channels 4*(id & 15) ..): coalesced 256-byte rows
+//   V: chunk id -> (key 2*(id >> 5) + (id & 1), channels 4*((id >> 1) & 15) ..): ADJACENT LANES hold the two keys of a
+//      pair for the same channels; they swap halves (one shuffle pair) so each lane owns 2 channels x 2 keys and writes
+//      (key 2p, key 2p+1) as one dword of the transposed image
+template <int NT>
+__device__ __forceinline__ void load_kv_f32(const float* __restrict__ k, long ldk, const float* __restrict__ v, long ldv, int j0, int Tk,
+                                            int tid, float4 (&kreg)[1024 / NT], float4 (&vreg)[1024 / NT]) {
+#pragma unroll
+    for (int i = 0; i < 1024 / NT; ++i) {
+        const int id = tid + i * NT;
+        const int kr = j0 + (id >> 4);
+        kreg[i] = kr < Tk ? *reinterpret_cast<const float4*>(k + (long)kr * ldk + (id & 15) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const int vr = j0 + 2 * (id >> 5) + (id & 1);
+        vreg[i] = vr < Tk ? *reinterpret_cast<const float4*>(v + (long)vr * ldv + ((id >> 1) & 15) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+// chunk id of the V tile after the pair swap: channels d0, d0 + 1 of keys (2 kp, 2 kp + 1) as packed hi / lo dwords h0 / l0,
+// h1 / l1.  Where they go in the V^T image is the caller's: the two kernels keep different key orders.
+struct VPair { int d0, kp; unsigned h0, l0, h1, l1; };
+__device__ __forceinline__ VPair v_pair_swap(int id, const float4& vr) {
+    const int par = id & 1, cc = (id >> 1) & 15;
+    // even lane keeps channels 4cc, 4cc+1 and receives them of key 2kp+1; odd lane keeps 4cc+2, 4cc+3
+    const float s0 = par ? vr.x : vr.z, s1 = par ? vr.y : vr.w;
+    const float r0 = __shfl_xor(s0, 1, 64), r1 = __shfl_xor(s1, 1, 64);
+    const float a0 = par ? r0 : vr.x, b0 = par ? vr.z : r0;     // channel d0: (key 2kp, key 2kp+1)
+    const float a1 = par ? r1 : vr.y, b1 = par ? vr.w : r1;     // channel d0 + 1
+    const unsigned h0 = pack_bf16x2(a0, b0), h1 = pack_bf16x2(a1, b1);
+    const unsigned l0 = pack_bf16x2(a0 - __uint_as_float(h0 << 16), b0 - __uint_as_float(h0 & 0xffff0000u));
+    const unsigned l1 = pack_bf16x2(a1 - __uint_as_float(h1 << 16), b1 - __uint_as_float(h1 & 0xffff0000u));
+    return {4 * cc + 2 * par, id >> 5, h0, l0, h1, l1};
+}
+__device__ __forceinline__ void store_v_pair(char* Vh, char* Vl, int o0, int o1, const VPair& p) {
+    *reinterpret_cast<unsigned*>(Vh + o0) = p.h0;
+    *reinterpret_cast<unsigned*>(Vl + o0) = p.l0;
+    *reinterpret_cast<unsigned*>(Vh + o1) = p.h1;
+    *reinterpret_cast<unsigned*>(Vl + o1) = p.l1;
 }
 
 // PRE = false: q / k / v fp32 row-major, split (and V transposed) by this kernel tile by tile.
@@ -60,22 +113,20 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
     char* Vl = Vh + 2 * TILE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, l16 = lane & 15;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int pair = (slot / nq) * 8 + xcd;            // XCD-aware: the query tiles of one (batch, head) share an L2
-    if (pair >= npairs) return;
-    const int qt = slot % nq;
-    const int b = pair / nheads, h = pair % nheads;
-    const int qb = q_begin + qt * (NW * QW) + wave * QW;
+    const PairTile pt = pair_tile(nq, nheads, npairs);
+    if (!pt.valid) return;
+    const int b = pt.b, h = pt.h;
+    const int q0 = q_begin + pt.qt * (NW * QW), qb = q0 + wave * QW;   // the workgroup's, this wave's first query
     q += (long)b * q_bs + h * D;
     k += (long)b * k_bs + h * D;
     v += PRE ? (long)b * v_bs + (long)h * D * ldv : (long)b * v_bs + h * D;
     out += (long)b * o_bs + h * D;
     const float* km = keymask ? keymask + (long)b * km_bs : nullptr;
     const float sc2 = scale * 1.44269504088896341f;
-    const int Tk = klen ? (klen[b] < Tn ? klen[b] : Tn) : Tn;
-    if (klen && q_begin + qt * (NW * QW) >= Tk) {        // a workgroup of pure padding rows
+    const auto [Tk, kend, ntile, vis_all] = key_window(Tn, klen, b, chunk, q0, NW * QW);
+    if (klen && q0 >= Tk) {                            // a workgroup of pure padding rows
         for (int id = tid; id < NW * QW * 16; id += 64 * NW) {
-            const int i = q_begin + qt * (NW * QW) + (id >> 4);
+            const int i = q0 + (id >> 4);
             if (i < Tn) *reinterpret_cast<float4*>(out + (long)i * ldo + (id & 15) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         return;
@@ -95,13 +146,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
                 aql[mf][ks] = *reinterpret_cast<const short8_t*>(qp + 1024);
             } else {
                 const float* qp = reinterpret_cast<const float*>(q) + (long)row * ldq + ks * 32 + 8 * g;
-                const float4 a = *reinterpret_cast<const float4*>(qp), c = *reinterpret_cast<const float4*>(qp + 4);
-                const float x0[4] = {a.x, a.y, a.z, a.w}, x1[4] = {c.x, c.y, c.z, c.w};
-                uint2 h0, l0, h1, l1;
-                split4(x0, h0, l0);
-                split4(x1, h1, l1);
-                aqh[mf][ks] = __builtin_bit_cast(short8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
-                aql[mf][ks] = __builtin_bit_cast(short8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));
+                split8(*reinterpret_cast<const float4*>(qp), *reinterpret_cast<const float4*>(qp + 4), aqh[mf][ks], aql[mf][ks]);
             }
         }
     }
@@ -114,30 +159,9 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
         for (int i = 0; i < 4; ++i) o[mf][i] = float4_t{0.f, 0.f, 0.f, 0.f};
         m_run[mf] = -INFINITY;
         l_run[mf] = 0.f;
-        const int i = qb + mf * 16 + l16;
-        int e = Tk;
-        if (chunk > 0) { int c2 = (i / chunk + 1) * chunk; e = c2 < e ? c2 : e; }
-        lim[mf] = e;
-    }
-    int kend = Tk;
-    if (chunk > 0) {
-        int qlast = q_begin + qt * (NW * QW) + NW * QW - 1;
-        if (qlast > Tn - 1) qlast = Tn - 1;
-        int e = (qlast / chunk + 1) * chunk;
-        if (e < kend) kend = e;
-    }
-    const int ntile = (kend + KT - 1) / KT;
-    int vis_all = Tk;
-    if (chunk > 0) {
-        const int e = ((q_begin + qt * (NW * QW)) / chunk + 1) * chunk;
-        if (e < vis_all) vis_all = e;
+        lim[mf] = lane_limit(qb + mf * 16 + l16, chunk, Tk);
     }
 
-    // tile loads: 1024 chunks of 4 floats per operand, 4 per thread.
-    //   K: chunk id -> (key r = id >> 4, channels 4*(id & 15) ..): coalesced 256-byte rows
-    //   V: chunk id -> (key 2*(id >> 5) + (id & 1), channels 4*((id >> 1) & 15) ..): ADJACENT LANES hold the two keys of a
-    //      pair for the same channels; they swap halves (one shuffle pair) so each lane owns 2 channels x 2 keys and writes
-    //      (key 2p, key 2p+1) as one dword of the transposed image
     constexpr int NT = 64 * NW, CPT = 1024 / NT;       // threads; fp32 chunks (or 2 x bf16 chunks) per thread, tile and operand
     float4 kreg[CPT], vreg[CPT];
     auto load_tiles = [&](int j0) {
@@ -157,15 +181,8 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
                     vreg[2 * pi + pl] = (j0 + c < Tk) ? *reinterpret_cast<const float4*>(vb + (long)pl * 512 * ldv + (long)r * ldv + j0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
             }
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < CPT; ++i) {
-            const int id = tid + i * NT;
-            const int kr = j0 + (id >> 4);
-            kreg[i] = kr < Tk ? *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(k) + (long)kr * ldk + (id & 15) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const int vr = j0 + 2 * (id >> 5) + (id & 1);
-            vreg[i] = vr < Tk ? *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(v) + (long)vr * ldv + ((id >> 1) & 15) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            load_kv_f32<NT>(reinterpret_cast<const float*>(k), ldk, reinterpret_cast<const float*>(v), ldv, j0, Tk, tid, kreg, vreg);
         }
     };
     auto store_tiles = [&](int buf) {
@@ -189,7 +206,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
 #pragma unroll
         for (int i = 0; i < CPT; ++i) {
             const int id = tid + i * NT;
-            {
+            {                                          // (the K store stays in both kernels: as a helper it changes their registers)
                 const int r = id >> 4, c4 = id & 15;   // 4 channels = half a 16-byte chunk of bf16
                 const float x[4] = {kreg[i].x, kreg[i].y, kreg[i].z, kreg[i].w};
                 uint2 hi, lo;
@@ -198,25 +215,10 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
                 *reinterpret_cast<uint2*>(Kh + off) = hi;
                 *reinterpret_cast<uint2*>(Kl + off) = lo;
             }
-            {
-                const int par = id & 1, cc = (id >> 1) & 15, kp = id >> 5;
-                // even lane keeps channels 4cc, 4cc+1 and receives them of key 2kp+1; odd lane keeps 4cc+2, 4cc+3
-                const float s0 = par ? vreg[i].x : vreg[i].z, s1 = par ? vreg[i].y : vreg[i].w;
-                const float r0 = __shfl_xor(s0, 1, 64), r1 = __shfl_xor(s1, 1, 64);
-                const float a0 = par ? r0 : vreg[i].x, b0 = par ? vreg[i].z : r0;     // channel d0: (key 2kp, key 2kp+1)
-                const float a1 = par ? r1 : vreg[i].y, b1 = par ? vreg[i].w : r1;     // channel d0 + 1
-                const int d0 = 4 * cc + 2 * par;
-                const unsigned h0 = pack_bf16x2(a0, b0), h1 = pack_bf16x2(a1, b1);
-                const unsigned l0 = pack_bf16x2(a0 - __uint_as_float(h0 << 16), b0 - __uint_as_float(h0 & 0xffff0000u));
-                const unsigned l1 = pack_bf16x2(a1 - __uint_as_float(h1 << 16), b1 - __uint_as_float(h1 & 0xffff0000u));
-                // keys 2kp, 2kp + 1 = 32 ks + 16 hf + 4 gk + (0 | 2), + 1: slot 4 ks + gk, half hf, dword kp & 1
-                const int vs = 4 * (kp >> 4) + ((kp >> 1) & 3), vb = ((kp >> 3) & 1) * 8 + (kp & 1) * 4;
-                const int o0 = buf * TILE + swz(d0, vs) + vb, o1 = buf * TILE + swz(d0 + 1, vs) + vb;
-                *reinterpret_cast<unsigned*>(Vh + o0) = h0;
-                *reinterpret_cast<unsigned*>(Vl + o0) = l0;
-                *reinterpret_cast<unsigned*>(Vh + o1) = h1;
-                *reinterpret_cast<unsigned*>(Vl + o1) = l1;
-            }
+            const VPair p = v_pair_swap(id, vreg[i]);
+            // keys 2kp, 2kp + 1 = 32 ks + 16 hf + 4 gk + (0 | 2), + 1: slot 4 ks + gk, half hf, dword kp & 1
+            const int vs = 4 * (p.kp >> 4) + ((p.kp >> 1) & 3), vb = ((p.kp >> 3) & 1) * 8 + (p.kp & 1) * 4;
+            store_v_pair(Vh, Vl, buf * TILE + swz(p.d0, vs) + vb, buf * TILE + swz(p.d0 + 1, vs) + vb, p);
         }
     };
     load_tiles(0);
@@ -265,23 +267,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
             for (int nf = 0; nf < 4; ++nf)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[mf][nf][r]);
-            mx *= sc2;
-            float m_use = m_run[mf];
-            const bool grow = (mx - m_run[mf]) > 6.0f || m_run[mf] == -INFINITY;     // lazy rescale (see attention.hip)
-            if (__any(grow)) {
-                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const float m_new = fmaxf(m_run[mf], mx);
-                const float m_safe = m_new == -INFINITY ? 0.f : m_new;
-                const float alpha = __builtin_amdgcn_exp2f(m_run[mf] - m_safe);
-                l_run[mf] *= alpha;
-#pragma unroll
-                for (int df = 0; df < 4; ++df)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[mf][df][r] *= alpha;
-                m_run[mf] = m_new;
-                m_use = m_safe;
-            }
+            const float m_use = lazy_rescale(mx * sc2, m_run[mf], l_run[mf], o[mf]);
             float rs = 0.f;
 #pragma unroll
             for (int nf = 0; nf < 4; ++nf) {
@@ -320,10 +306,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
             }
     }
 #pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-        l_run[mf] += __shfl_xor(l_run[mf], 16, 64);
-        l_run[mf] += __shfl_xor(l_run[mf], 32, 64);
-    }
+    for (int mf = 0; mf < MF; ++mf) row_sum(l_run[mf]);
 #pragma unroll
     for (int mf = 0; mf < MF; ++mf) {
         const int i = qb + mf * 16 + l16;
@@ -339,8 +322,8 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_x_kernel(
 // ------------------------------------------------------------------------------------------ rel-pos attention, split build
 // Conformer encoder attention (speech/cosyvoice/transformer/attention.py:215-330, RelPositionMultiHeadedAttention) of the split
 // build on the MFMA:   score(i, j) = ((q_i + u) . k_j + (q_i + v) . p[T - 1 - i + j]) * scale,   p = linear_pos(pos_emb), 2T - 1
-// rows (rel_shift folded into the index).  attn_flash_x_kernel<1, false, 4> (fp32 q / k / v rows, split into bf16 hi + lo tile by
-// tile, three MFMAs per product) plus the position term of attn_relpos_kernel (csrc/attention.hip): per 64-key tile the wave's
+// rows (rel_shift folded into the index).  The operands of attn_flash_x_kernel<1, false, 4> (fp32 q / k / v rows, split into bf16
+// hi + lo tile by tile, three MFMAs per product; P goes through a per-wave LDS patch here) plus the position term of attn_relpos_kernel (csrc/attention.hip): per 64-key tile the wave's
 // 79-row window of p (fp32 rows, split like every other operand) times (q + v), five 16x16x32 fragment pairs x 3 MFMAs, shifted
 // per lane through the wave's fp32 LDS patch.  Replaces attn_dense_kernel<float> (fp32 VALU, 416 us per batched launch).
 __global__ __launch_bounds__(256) void attn_relpos_x_kernel(
@@ -360,19 +343,17 @@ __global__ __launch_bounds__(256) void attn_relpos_x_kernel(
     float* Bp = reinterpret_cast<float*>(Pl + NW * QW * 128);   // [4 waves][16][BW] position-term patch
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, l16 = lane & 15;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int pair = (slot / nq) * 8 + xcd;
-    if (pair >= npairs) return;
-    const int qt = slot % nq;
-    const int b = pair / nheads, h = pair % nheads;
-    const int qb = qt * (NW * QW) + wave * QW;
+    const PairTile pt = pair_tile(nq, nheads, npairs);
+    if (!pt.valid) return;
+    const int b = pt.b, h = pt.h;
+    const int q0 = pt.qt * (NW * QW), qb = q0 + wave * QW;
     q += (long)b * q_bs + h * D;
     k += (long)b * k_bs + h * D;
     v += (long)b * v_bs + h * D;
     out += (long)b * o_bs + h * D;
     pos += h * D;
     const float sc2 = scale * 1.44269504088896341f;
-    const int Tk = klen ? (klen[b] < Tn ? klen[b] : Tn) : Tn;
+    const auto [Tk, kend, ntile, vis_all] = key_window(Tn, klen, b, chunk, q0, NW * QW);
 
     // (q + u) and (q + v) fragments, hi + lo: lane (query l16, k-group g) holds [ks*32 + 8g .. +7]
     short8_t auh[2], aul[2], avh[2], avl[2];
@@ -386,59 +367,26 @@ __global__ __launch_bounds__(256) void attn_relpos_x_kernel(
             const float* pu = pos_u + h * D + ks * 32 + 8 * g;
             const float* pv = pos_v + h * D + ks * 32 + 8 * g;
             const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-            float xu0[4], xu1[4], xv0[4], xv1[4];
+            float xu[8], xv[8];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                xu0[e] = x[e] + pu[e]; xu1[e] = x[4 + e] + pu[4 + e];
-                xv0[e] = x[e] + pv[e]; xv1[e] = x[4 + e] + pv[4 + e];
-            }
-            uint2 h0, l0, h1, l1;
-            split4(xu0, h0, l0);
-            split4(xu1, h1, l1);
-            auh[ks] = __builtin_bit_cast(short8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
-            aul[ks] = __builtin_bit_cast(short8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));
-            split4(xv0, h0, l0);
-            split4(xv1, h1, l1);
-            avh[ks] = __builtin_bit_cast(short8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
-            avl[ks] = __builtin_bit_cast(short8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));
+            for (int e = 0; e < 8; ++e) { xu[e] = x[e] + pu[e]; xv[e] = x[e] + pv[e]; }
+            split8(xu, auh[ks], aul[ks]);
+            split8(xv, avh[ks], avl[ks]);
         }
     }
     float4_t o[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) o[i] = float4_t{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
-    int lim = Tk;
-    if (chunk > 0) { const int c2 = ((qb + l16) / chunk + 1) * chunk; lim = c2 < lim ? c2 : lim; }
-    int kend = Tk;
-    if (chunk > 0) {
-        int qlast = qt * (NW * QW) + NW * QW - 1;
-        if (qlast > Tn - 1) qlast = Tn - 1;
-        const int e = (qlast / chunk + 1) * chunk;
-        if (e < kend) kend = e;
-    }
-    const int ntile = (kend + KT - 1) / KT;
-    int vis_all = Tk;
-    if (chunk > 0) {
-        const int e = ((qt * (NW * QW)) / chunk + 1) * chunk;
-        if (e < vis_all) vis_all = e;
-    }
+    const int lim = lane_limit(qb + l16, chunk, Tk);
     char* Pwh = Ph + wave * QW * 128;
     char* Pwl = Pl + wave * QW * 128;
     float* Bw = Bp + wave * 16 * BW;
 
     constexpr int NT = 64 * NW, CPT = 1024 / NT;
     float4 kreg[CPT], vreg[CPT];
-    auto load_tiles = [&](int j0) {
-#pragma unroll
-        for (int i = 0; i < CPT; ++i) {
-            const int id = tid + i * NT;
-            const int kr = j0 + (id >> 4);
-            kreg[i] = kr < Tk ? *reinterpret_cast<const float4*>(k + (long)kr * ldk + (id & 15) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const int vr = j0 + 2 * (id >> 5) + (id & 1);
-            vreg[i] = vr < Tk ? *reinterpret_cast<const float4*>(v + (long)vr * ldv + ((id >> 1) & 15) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store_tiles = [&](int buf) {                  // as attn_flash_x_kernel<.., PRE = false, ..>: split K, transpose + split V
+    auto load_tiles = [&](int j0) { load_kv_f32<NT>(k, ldk, v, ldv, j0, Tk, tid, kreg, vreg); };
+    auto store_tiles = [&](int buf) {                  // K as attn_flash_x_kernel<.., PRE = false, ..>; V^T in the natural key order
 #pragma unroll
         for (int i = 0; i < CPT; ++i) {
             const int id = tid + i * NT;
@@ -451,22 +399,10 @@ __global__ __launch_bounds__(256) void attn_relpos_x_kernel(
                 *reinterpret_cast<uint2*>(Kh + off) = hi;
                 *reinterpret_cast<uint2*>(Kl + off) = lo;
             }
-            {
-                const int par = id & 1, cc = (id >> 1) & 15, kp = id >> 5;
-                const float s0 = par ? vreg[i].x : vreg[i].z, s1 = par ? vreg[i].y : vreg[i].w;
-                const float r0 = __shfl_xor(s0, 1, 64), r1 = __shfl_xor(s1, 1, 64);
-                const float a0 = par ? r0 : vreg[i].x, b0 = par ? vreg[i].z : r0;
-                const float a1 = par ? r1 : vreg[i].y, b1 = par ? vreg[i].w : r1;
-                const int d0 = 4 * cc + 2 * par;
-                const unsigned h0 = pack_bf16x2(a0, b0), h1 = pack_bf16x2(a1, b1);
-                const unsigned l0 = pack_bf16x2(a0 - __uint_as_float(h0 << 16), b0 - __uint_as_float(h0 & 0xffff0000u));
-                const unsigned l1 = pack_bf16x2(a1 - __uint_as_float(h1 << 16), b1 - __uint_as_float(h1 & 0xffff0000u));
-                const int o0 = buf * TILE + swz(d0, kp >> 2) + (kp & 3) * 4, o1 = buf * TILE + swz(d0 + 1, kp >> 2) + (kp & 3) * 4;
-                *reinterpret_cast<unsigned*>(Vh + o0) = h0;
-                *reinterpret_cast<unsigned*>(Vl + o0) = l0;
-                *reinterpret_cast<unsigned*>(Vh + o1) = h1;
-                *reinterpret_cast<unsigned*>(Vl + o1) = l1;
-            }
+            const VPair p = v_pair_swap(id, vreg[i]);
+            // the V^T image in the natural key order (P goes through LDS here): keys 2kp, 2kp + 1 = dword kp of the row
+            const int vo = (p.kp & 3) * 4;
+            store_v_pair(Vh, Vl, buf * TILE + swz(p.d0, p.kp >> 2) + vo, buf * TILE + swz(p.d0 + 1, p.kp >> 2) + vo, p);
         }
     };
     // the position window of tile j0: rows mbase + f*16 + l16 (clamped: rows outside [0, 2T-2] only meet masked pairs), fp32, read
@@ -503,13 +439,8 @@ __global__ __launch_bounds__(256) void attn_relpos_x_kernel(
             bd[f] = float4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const float x0[4] = {praw[f][ks][0].x, praw[f][ks][0].y, praw[f][ks][0].z, praw[f][ks][0].w};
-                const float x1[4] = {praw[f][ks][1].x, praw[f][ks][1].y, praw[f][ks][1].z, praw[f][ks][1].w};
-                uint2 h0, l0, h1, l1;
-                split4(x0, h0, l0);
-                split4(x1, h1, l1);
-                const short8_t ph = __builtin_bit_cast(short8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
-                const short8_t pl = __builtin_bit_cast(short8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));
+                short8_t ph, pl;
+                split8(praw[f][ks][0], praw[f][ks][1], ph, pl);
                 bd[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, avh[ks], bd[f], 0, 0, 0);
                 bd[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, avl[ks], bd[f], 0, 0, 0);
                 bd[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl, avh[ks], bd[f], 0, 0, 0);
@@ -558,23 +489,7 @@ __global__ __launch_bounds__(256) void attn_relpos_x_kernel(
                 }
                 mx = fmaxf(mx, x);
             }
-        mx *= sc2;
-        float m_use = m_run;
-        const bool grow = (mx - m_run) > 6.0f || m_run == -INFINITY;
-        if (__any(grow)) {
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);
-            const float m_safe = m_new == -INFINITY ? 0.f : m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_safe);
-            l_run *= alpha;
-#pragma unroll
-            for (int df = 0; df < 4; ++df)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[df][r] *= alpha;
-            m_run = m_new;
-            m_use = m_safe;
-        }
+        const float m_use = lazy_rescale(mx * sc2, m_run, l_run, o);
         float rs = 0.f;
 #pragma unroll
         for (int nf = 0; nf < 4; ++nf) {
@@ -611,8 +526,7 @@ __global__ __launch_bounds__(256) void attn_relpos_x_kernel(
             }
         __builtin_amdgcn_wave_barrier();
     }
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
+    row_sum(l_run);
     const int i = qb + l16;
     if (i < Tn) {
         const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
@@ -645,9 +559,9 @@ extern "C" int mmx_attn_flash_x(const float* q, int64_t ldq, int64_t q_bs, const
     MMX_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && q_bs % 4 == 0 && k_bs % 4 == 0 && v_bs % 4 == 0 && o_bs % 4 == 0);
     MMX_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 16) == 0);
     const int npairs = H * B, Tq = T_ - q_begin;
-    const bool small = (long)npairs * ((Tq + 127) / 128) < 192;         // fewer 128-query tiles than ~3/4 of the CUs
+    const bool small = few_tiles(npairs, Tq);
     const int qtile = small ? 64 : 128, nq = (Tq + qtile - 1) / qtile;
-    dim3 grid(8 * ((npairs + 7) / 8) * nq);
+    const dim3 grid = pair_grid(npairs, nq);
     if (small) return launch_flash_x<1, false, 4>(grid, stream, q, ldq, q_bs, k, ldk, k_bs, v, ldv, v_bs, out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq, H, npairs, q_begin, klen);
     return launch_flash_x<1, false, 8>(grid, stream, q, ldq, q_bs, k, ldk, k_bs, v, ldv, v_bs, out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq, H, npairs, q_begin, klen);
 }
@@ -662,9 +576,9 @@ extern "C" int mmx_attn_flash_xs(const void* qk, int64_t ldqk, int64_t qk_bs, co
     MMX_CHECK_ARG(ldqk >= 2048 && ldqk % 8 == 0 && qk_bs % 8 == 0 && ldvt % 8 == 0 && ldvt >= ((T_ + 7) / 8) * 8 && vt_bs % 8 == 0 && vt_bs >= 2 * 512 * ldvt);
     MMX_CHECK_ARG(ldo % 4 == 0 && o_bs % 4 == 0 && ((uintptr_t)qk % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)out % 16) == 0);
     const int npairs = H * B, Tq = T_ - q_begin;
-    const bool small = form == 3 || (long)npairs * ((Tq + 127) / 128) < 192;
+    const bool small = form == 3 || few_tiles(npairs, Tq);
     const int qtile = small ? 64 : 128, nq = (Tq + qtile - 1) / qtile;
-    dim3 grid(8 * ((npairs + 7) / 8) * nq);
+    const dim3 grid = pair_grid(npairs, nq);
     const bf16_t* q = (const bf16_t*)qk;
     // Every form holds 64 KB of LDS (K and V^T, hi + lo, double buffered); P stays in registers.  The 128-query workgroups
     // (<1, true, 8>, 114 registers per wave) are the form of every grid that is not small: two of them fit on a CU, and alone on
@@ -677,8 +591,7 @@ extern "C" int mmx_attn_flash_xs(const void* qk, int64_t ldqk, int64_t qk_bs, co
     // form 2: 256-query workgroups wherever the grid is not small; form 3: the 4-wave 64-query form everywhere.
     const int nq2 = (Tq + 255) / 256;
     if (!small && form == 2) {
-        dim3 grid2(8 * ((npairs + 7) / 8) * nq2);
-        return launch_flash_x<2, true, 8>(grid2, stream, q, ldqk, qk_bs, q + 512, ldqk, qk_bs, vt, ldvt, vt_bs, out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq2, H, npairs, q_begin, klen);
+        return launch_flash_x<2, true, 8>(pair_grid(npairs, nq2), stream, q, ldqk, qk_bs, q + 512, ldqk, qk_bs, vt, ldvt, vt_bs, out, ldo, o_bs, T_, scale, keymask, km_bs, chunk, nq2, H, npairs, q_begin, klen);
     }
     // (4 waves x 32 queries - the 256-query form's fragment reuse with one wave per SIMD - measured 118 us at 5 x 860
     // frames against 92: one wave per SIMD has nothing to overlap its softmax with)
@@ -700,7 +613,7 @@ extern "C" int mmx_attn_relpos_x(const float* q, int64_t ldq, int64_t q_bs, cons
     const int npairs = H * B, nq = (T_ + 63) / 64;
     const size_t lds = (size_t)8 * 64 * 128 + (size_t)2 * 4 * 16 * 128 + (size_t)4 * 16 * 84 * 4;
     MMX_LDS_OPT_IN(attn_relpos_x_kernel, lds);
-    hipLaunchKernelGGL(attn_relpos_x_kernel, dim3(8 * ((npairs + 7) / 8) * nq), dim3(256), lds, stream, q, ldq, q_bs, k, ldk, k_bs, v, ldv, v_bs,
+    hipLaunchKernelGGL(attn_relpos_x_kernel, pair_grid(npairs, nq), dim3(256), lds, stream, q, ldq, q_bs, k, ldk, k_bs, v, ldv, v_bs,
                        pos, ldp, pos_u, pos_v, out, ldo, o_bs, T_, scale, chunk, nq, H, npairs, klen);
     MMX_LAUNCH_CHECK();
     return MMX_OK;
