@@ -450,7 +450,8 @@ typedef struct MmxEstResnetParams {
  * attention rows in two K halves and the FF intermediate in 256-wide chunks (two bf16 planes of 64 rows fit LDS that way) and is
  * bit-identical to its 32-row tile;
  * waves = 4 (one wave per SIMD, 64-column slices) or 8 (two per SIMD, 32-column slices: one wave's epilogue runs under the
- * other's MFMA stage; bf16 only). */
+ * other's MFMA stage; bf16 only).  Any other value of a field (pf = 3, waves = 5, a bit above these, 512 for mmx_est_resnet) is MMX_EARG, as is a
+ * (dtype, bm, cfg) the build has no instantiation for; MMX_X2W takes the split build's default form, whatever cfg says. */
 int mmx_est_tail(const MmxEstTailParams* p, int dtype, int bm, int cfg, hipStream_t stream);
 int mmx_est_resnet(const MmxEstResnetParams* p, int dtype, int bm, int cfg, hipStream_t stream);
 /* ---------------------------------------------------------------------------------------------

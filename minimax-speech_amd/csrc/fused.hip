@@ -1237,23 +1237,48 @@ __global__ __launch_bounds__(256) void dac_ru_kernel(MmxDacRuParams p) {
     }
 }
 
-template <int C, int BM, int NS>
-size_t dac_ru_lds(int dil) {
-    constexpr int CP = (C + 31) / 32 * 32, PA = dac_pitch(CP);
-    return (size_t)NS * ((size_t)(BM + 6 * dil) * PA + (size_t)BM * PA) + 4 * DAC_PATCH_FLOATS * 4 + 8 * CP * 4;
+// ---------------------------------------------------------------------------------------------------------------
+// Host side.  Per kernel family: the dynamic LDS size, ONE launcher template, a table with one row per instantiation (a row and
+// its launcher come from one spelling of the template arguments, *_form<...>()) and a constexpr selection: request -> wanted
+// properties (the only place the defaults live) -> row, none = MMX_EARG.  The static_asserts under each selection are the record
+// of what the engines' default requests launch (mmx/flow.py and mmx/dac.py tile rules; tools/check_resources.py gates them).
+constexpr size_t LDS_MAX = 160 * 1024;
+constexpr size_t dac_ru_lds(int C, int bm, int ns, int dil) {
+    const int CP = (C + 31) / 32 * 32, PA = dac_pitch(CP);
+    return (size_t)ns * ((size_t)(bm + 6 * dil) * PA + (size_t)bm * PA) + 4 * DAC_PATCH_FLOATS * 4 + 8 * CP * 4;
 }
-
-template <typename T, int BM, int NW, int NS = 1>
-size_t tail_lds() {
-    if (NS == 2 && BM == 64 && sizeof(T) == 2)         // the split build's 64-row tile (HK in est_tail_tile)
-        return (size_t)NS * 2 * BM * tile_pitch(256, sizeof(T)) + (size_t)NW * SPATCH_FLOATS * 4 + (size_t)BM * NW * 4 + (size_t)TAIL_PRM_FLOATS * 4;
-    return NS * ((size_t)BM * tile_pitch(512, sizeof(T)) + (size_t)BM * tile_pitch(256, sizeof(T))) + (size_t)NW * PATCH_FLOATS * 4 + (size_t)BM * NW * 4 +
+constexpr size_t tail_lds(int esz, int bm, int nw, int ns) {
+    if (ns == 2 && bm == 64 && esz == 2)               // the split build's 64-row tile (HK in est_tail_tile)
+        return (size_t)ns * 2 * bm * tile_pitch(256, esz) + (size_t)nw * SPATCH_FLOATS * 4 + (size_t)bm * nw * 4 + (size_t)TAIL_PRM_FLOATS * 4;
+    return ns * ((size_t)bm * tile_pitch(512, esz) + (size_t)bm * tile_pitch(256, esz)) + (size_t)nw * PATCH_FLOATS * 4 + (size_t)bm * nw * 4 +
            (size_t)TAIL_PRM_FLOATS * 4;
 }
-template <typename T, int BM, int NW, int NS = 1>
-size_t resnet_lds(int cin) {
-    return NS * ((size_t)(BM + 18) * tile_pitch(cin, sizeof(T)) + (size_t)(BM + 16) * tile_pitch(256, sizeof(T))) + (size_t)NW * PATCH_FLOATS * 4 +
-           (size_t)(BM + 16) * NW * 4;
+constexpr size_t resnet_lds(int esz, int bm, int nw, int ns, int cin) {
+    return ns * ((size_t)(bm + 18) * tile_pitch(cin, esz) + (size_t)(bm + 16) * tile_pitch(256, esz)) + (size_t)nw * PATCH_FLOATS * 4 +
+           (size_t)(bm + 16) * nw * 4;
+}
+
+// a table row: what a request is matched on, and that instantiation's launcher (P: the entry point's parameter struct)
+template <typename P>
+struct Form {
+    int dtype;                                         // MMX_BF16 / MMX_X2 / MMX_F32; MMX_X2W is MMX_X2 with
+    bool wp;                                           // weight planes: every packed weight is [hi pack | lo pack]
+    int bm, nw, pf;                                    // rows, waves, ring depth
+    int pw, C;                                         // est_tail: n-fragments per pass (4, or 2 in the narrow 8-wave kernels); dac_ru: channels; else 0
+    int (*launch)(const P&, hipStream_t);
+};
+template <typename T, int NS>
+constexpr int form_dtype = sizeof(T) == 4 ? MMX_F32 : NS == 2 ? MMX_X2 : MMX_BF16;
+template <typename P, size_t N>
+constexpr const Form<P>* find_form(const Form<P> (&forms)[N], int dtype, bool wp, int bm, int nw, int pf, int pw, int C) {
+    for (const Form<P>& f : forms)
+        if (f.dtype == dtype && f.wp == wp && f.bm == bm && f.nw == nw && f.pf == pf && f.pw == pw && f.C == C) return &f;
+    return nullptr;
+}
+// the fields of cfg = pf + 16 * waves (+ the bits of `known` above them): any other value of a field is MMX_EARG
+constexpr bool cfg_fields_ok(int cfg, int known) {
+    const int pf = cfg & 15, nw = (cfg >> 4) & 15;
+    return cfg >= 0 && !(cfg & ~known) && (pf == 0 || pf == 2 || pf == 4 || pf == 8) && (nw == 0 || nw == 4 || nw == 8);
 }
 
 int check_next(const MmxEstNext& nx, int dtype, int T_) {
@@ -1276,6 +1301,164 @@ int check_next(const MmxEstNext& nx, int dtype, int T_) {
     return MMX_OK;
 }
 
+// ---- est_tail
+template <typename T, int BM, int PF, int NW, int NS, int PW, bool WP>
+int launch_tail(const MmxEstTailParams& p, hipStream_t stream) {
+    constexpr size_t lds = tail_lds(sizeof(T), BM, NW, NS);
+    MMX_CHECK_ARG(lds <= LDS_MAX);
+    // (OCC = 1: two 4-wave workgroups per CU measured slower everywhere and spilled; cfg bit 256 asked for them and is refused)
+    MMX_LDS_OPT_IN((est_tail_kernel<T, BM, PF, NW, NS, 1, PW, WP>), lds);
+    hipLaunchKernelGGL((est_tail_kernel<T, BM, PF, NW, NS, 1, PW, WP>), dim3((p.T - p.t_begin + BM - 1) / BM, p.B), dim3(64 * NW), lds, stream, p);
+    MMX_LAUNCH_CHECK();
+    return MMX_OK;
+}
+using TailForm = Form<MmxEstTailParams>;
+template <typename T, int BM, int PF, int NW, int NS = 1, int PW = 4, bool WP = false>
+constexpr TailForm tail_form() { return {form_dtype<T, NS>, WP, BM, NW, PF, PW, 0, launch_tail<T, BM, PF, NW, NS, PW, WP>}; }
+constexpr TailForm TAIL_FORMS[] = {
+    // bf16 build: narrow passes; 64-column passes (64 rows: the round-2 / round-3 forms, reached with an explicit cfg only)
+    tail_form<bf16_t, 64, 2, 8, 1, 2>(), tail_form<bf16_t, 32, 8, 8, 1, 2>(), tail_form<bf16_t, 32, 4, 8, 1, 2>(),
+    tail_form<bf16_t, 64, 4, 4>(), tail_form<bf16_t, 64, 2, 4>(), tail_form<bf16_t, 32, 4, 8>(), tail_form<bf16_t, 32, 2, 8>(),
+    tail_form<bf16_t, 32, 2, 4>(), tail_form<bf16_t, 32, 4, 4>(), tail_form<bf16_t, 16, 4, 8>(), tail_form<bf16_t, 16, 8, 4>(),
+    // split build: two bf16 planes per LDS tile, so the largest 64-column-pass tile is 32 rows (137 KB with 8 waves), and it has no
+    // ring 4 k-steps deep (measured no faster: 35.7 / 38.5 / 54.6 us at 32 / 128 / 256 workgroups against 37.4 / 40.4 / 55.2 - the
+    // stages are bound by the CU's L2 read rate, not by the latency of the loads in flight: profiles/r04_tail_lab_x.txt);
+    // 64 rows: two planes fit with the attention tile in K halves and 256-wide FF chunks (est_tail_tile, HK), narrow passes only
+    tail_form<bf16_t, 64, 2, 8, 2, 2>(), tail_form<bf16_t, 64, 4, 8, 2, 2>(), tail_form<bf16_t, 32, 2, 8, 2, 2>(), tail_form<bf16_t, 32, 4, 8, 2, 2>(),
+    tail_form<bf16_t, 32, 2, 8, 2>(), tail_form<bf16_t, 32, 4, 4, 2>(), tail_form<bf16_t, 16, 4, 8, 2>(), tail_form<bf16_t, 16, 8, 4, 2>(),
+    // split build, weight planes (the default tiles); fp32 build
+    tail_form<bf16_t, 64, 2, 8, 2, 2, true>(), tail_form<bf16_t, 32, 2, 8, 2, 4, true>(), tail_form<bf16_t, 16, 4, 8, 2, 4, true>(),
+    tail_form<float, 32, 4, 4>(), tail_form<float, 16, 8, 4>(),
+};
+// cfg = pf + 16 * waves + 512 * narrow; bits 256 and 1024 are retired.  dtype: MMX_X2 for MMX_X2W, which sets wp
+constexpr const TailForm* tail_select(int dtype, bool wp, int bm, int cfg) {
+    if (!cfg_fields_ok(cfg, 0x7ff) || (bm != 16 && bm != 32 && bm != 64)) return nullptr;
+    if (wp) cfg = 0;                                   // weight planes: the split build's default tiles, whatever cfg says
+    // (256: two 4-wave workgroups per CU, 1024: two row tiles per workgroup: removed, see est_tail_kernel)
+    if (cfg & (256 | 1024)) return nullptr;
+    int pf = cfg & 15, nw = (cfg >> 4) & 15;
+    bool narrow = (cfg >> 9) & 1;                      // 8 waves, 32-column passes (PW = 2)
+    // library defaults of the bf16 build (cfg = 0): the narrow-pass 8-wave kernels for the 64- and 32-row tiles (measured per
+    // launch at 10 000 rows: 51.1 us against 58.7 us with 4 waves x 64-column passes; 32 rows, 4 000 rows: 31.8 against 33.0)
+    if (cfg == 0 && dtype == MMX_BF16 && bm >= 32) { narrow = true; pf = bm == 64 ? 2 : 8; }
+    if (dtype == MMX_X2 && bm == 64) narrow = true;    // the split 64-row tile has narrow passes only
+    // waves: the narrow kernels have 8 whatever the field says.  Split build: 8 by default for every tile - each then sums its
+    // LayerNorms alike and an utterance's bits do not depend on the tile height its flow group was given; 4 with an explicit cfg
+    if (narrow) nw = 8;
+    else if (nw == 0) nw = dtype == MMX_X2 || (dtype == MMX_BF16 && bm == 32) ? 8 : 4;
+    // ring depth: the one asked for where the tile has a form with it, otherwise the tile's own: MF * PF k-step fragments in
+    // flight per wave whatever the height (stage_run: 2 for 64 rows .. 8 for 16), half of that with 8 waves x 64-column passes
+    const int pw = narrow ? 2 : 4, pf_tile = narrow ? 128 / bm : 512 / (bm * nw);
+    const TailForm* f = find_form(TAIL_FORMS, dtype, wp, bm, nw, pf, pw, 0);
+    return f ? f : find_form(TAIL_FORMS, dtype, wp, bm, nw, pf_tile, pw, 0);
+}
+// the defaults (cfg = 0) of every build and tile height
+static_assert(tail_select(MMX_BF16, false, 64, 0)->launch == launch_tail<bf16_t, 64, 2, 8, 1, 2, false> && tail_select(MMX_BF16, false, 32, 0)->launch == launch_tail<bf16_t, 32, 8, 8, 1, 2, false>);
+static_assert(tail_select(MMX_BF16, false, 16, 0)->launch == launch_tail<bf16_t, 16, 8, 4, 1, 4, false> && tail_select(MMX_X2, false, 64, 0)->launch == launch_tail<bf16_t, 64, 2, 8, 2, 2, false>);
+static_assert(tail_select(MMX_X2, false, 32, 0)->launch == launch_tail<bf16_t, 32, 2, 8, 2, 4, false> && tail_select(MMX_X2, false, 16, 0)->launch == launch_tail<bf16_t, 16, 4, 8, 2, 4, false>);
+static_assert(tail_select(MMX_X2, true, 64, 0)->launch == launch_tail<bf16_t, 64, 2, 8, 2, 2, true> && tail_select(MMX_X2, true, 32, 0)->launch == launch_tail<bf16_t, 32, 2, 8, 2, 4, true>);
+static_assert(tail_select(MMX_X2, true, 16, 0)->launch == launch_tail<bf16_t, 16, 4, 8, 2, 4, true>);
+static_assert(tail_select(MMX_F32, false, 32, 0)->launch == launch_tail<float, 32, 4, 4, 1, 4, false> && tail_select(MMX_F32, false, 16, 0)->launch == launch_tail<float, 16, 8, 4, 1, 4, false>);
+
+// ---- est_resnet
+template <typename T, int BM, int PF, int NW, int NS, bool WP>
+int launch_resnet(const MmxEstResnetParams& p, hipStream_t stream) {
+    const size_t lds = resnet_lds(sizeof(T), BM, NW, NS, p.cin);
+    MMX_CHECK_ARG(lds <= LDS_MAX);
+    MMX_LDS_OPT_IN((est_resnet_kernel<T, BM, PF, NW, NS, WP>), lds);
+    hipLaunchKernelGGL((est_resnet_kernel<T, BM, PF, NW, NS, WP>), dim3((p.T - p.t_begin + BM - 1) / BM, p.B), dim3(64 * NW), lds, stream, p);
+    MMX_LAUNCH_CHECK();
+    return MMX_OK;
+}
+using ResnetForm = Form<MmxEstResnetParams>;
+template <typename T, int BM, int PF, int NW, int NS = 1, bool WP = false>
+constexpr ResnetForm resnet_form() { return {form_dtype<T, NS>, WP, BM, NW, PF, 0, 0, launch_resnet<T, BM, PF, NW, NS, WP>}; }
+constexpr ResnetForm RESNET_FORMS[] = {
+    // bf16 build: 8 waves, 4 waves; fp32 build
+    resnet_form<bf16_t, 64, 2, 8>(), resnet_form<bf16_t, 32, 4, 8>(), resnet_form<bf16_t, 32, 2, 8>(), resnet_form<bf16_t, 16, 4, 8>(), resnet_form<bf16_t, 16, 2, 8>(),
+    resnet_form<bf16_t, 64, 4, 4>(), resnet_form<bf16_t, 64, 2, 4>(), resnet_form<bf16_t, 32, 4, 4>(), resnet_form<bf16_t, 32, 2, 4>(),
+    resnet_form<bf16_t, 16, 8, 4>(), resnet_form<bf16_t, 16, 4, 4>(), resnet_form<bf16_t, 16, 2, 4>(),
+    resnet_form<float, 16, 8, 4>(), resnet_form<float, 16, 4, 4>(), resnet_form<float, 16, 2, 4>(),
+    // split build (two bf16 planes per LDS tile): 32-row tiles while the input tile leaves room (cin <= 320: 150 KB with 4 waves),
+    // 16 rows for the 512-channel input of the up block; then the same with weight planes
+    resnet_form<bf16_t, 32, 4, 8, 2>(), resnet_form<bf16_t, 32, 2, 8, 2>(), resnet_form<bf16_t, 32, 4, 4, 2>(), resnet_form<bf16_t, 32, 2, 4, 2>(),
+    resnet_form<bf16_t, 16, 4, 8, 2>(), resnet_form<bf16_t, 16, 2, 8, 2>(), resnet_form<bf16_t, 16, 4, 4, 2>(), resnet_form<bf16_t, 16, 2, 4, 2>(),
+    resnet_form<bf16_t, 32, 4, 8, 2, true>(), resnet_form<bf16_t, 32, 2, 8, 2, true>(), resnet_form<bf16_t, 32, 4, 4, 2, true>(), resnet_form<bf16_t, 32, 2, 4, 2, true>(),
+    resnet_form<bf16_t, 16, 4, 8, 2, true>(), resnet_form<bf16_t, 16, 2, 8, 2, true>(), resnet_form<bf16_t, 16, 4, 4, 2, true>(), resnet_form<bf16_t, 16, 2, 4, 2, true>(),
+};
+// ring depth: the deepest of 8 / 4 / 2, starting at `want`, that divides every stage's k-step count (conv k3 over cin, conv k3
+// over 256, 1x1 over cin, Q/K/V over 256); cin = 320 allows 2 (bf16) / 4 (fp32) only.  0: not even 2 does (MMX_EARG).
+constexpr int ring_depth(int want, int cin, int kb) {
+    int pf = want;
+    while (pf > 2 && ((3 * cin / kb) % pf || (cin / kb) % pf || (256 / kb) % pf)) pf /= 2;
+    return (cin / kb) % 2 == 0 ? pf : 0;
+}
+// cfg = pf + 16 * waves.  dtype: MMX_X2 for MMX_X2W, which sets wp.  cin: a multiple of 32 in 64 .. 512 (mmx_est_resnet checks it)
+constexpr const ResnetForm* resnet_select(int dtype, bool wp, int bm, int cfg, int cin) {
+    if (!cfg_fields_ok(cfg, 0xff)) return nullptr;
+    int nw = cfg >> 4;
+    // Split build: 8 waves (two per SIMD: a wave alone on its SIMD issues vector instructions at half the SIMD's rate, and the
+    // epilogues here are vector work) where the per-wave patches still fit beside the two-plane tiles: cin = 256, the twelve mid
+    // blocks.  The 16-row tile asks that of the 32-ROW tile's size: both tile heights then sum every LayerNorm alike - bit-identical.
+    // (An explicit waves = 8 without that room gets 4 waves, not an error.)
+    if (dtype == MMX_X2) nw = nw != 4 && resnet_lds(2, 32, 8, 2, cin) <= LDS_MAX ? 8 : 4;
+    // bf16 build: 8 waves (two per SIMD) measured faster for the 64-row ResNet tile (50.6 vs 59.7 us at 14 336 rows); they need 17 KB
+    // more LDS for the per-wave patches, which the 512-channel input tile (up block) does not leave
+    // (and for the smaller tiles: 31.7 vs 36.2 us at 32 rows, 26.9 vs 29.0 us at 16 rows)
+    else if (nw == 0) nw = dtype == MMX_BF16 && resnet_lds(2, bm, 8, 1, cin) <= LDS_MAX ? 8 : 4;
+    // the tile's form with the deepest ring the rule allows; asked for nothing, the deepest the tile has
+    for (int pf = ring_depth(cfg & 15 ? cfg & 15 : 8, cin, dtype == MMX_F32 ? 16 : 32); pf >= 2; pf /= 2)
+        if (const ResnetForm* f = find_form(RESNET_FORMS, dtype, wp, bm, nw, pf, 0, 0)) return f;
+    return nullptr;
+}
+// the defaults (cfg = 0) at the estimator's input widths, cin = 256 (mid blocks), 320 (first block) and 512 (up block; split build: 16 rows);
+// cfg = 16 * 4: the 4-wave request of the lab tools
+static_assert(resnet_select(MMX_BF16, false, 64, 0, 256)->launch == launch_resnet<bf16_t, 64, 2, 8, 1, false> && resnet_select(MMX_BF16, false, 32, 0, 256)->launch == launch_resnet<bf16_t, 32, 4, 8, 1, false>);
+static_assert(resnet_select(MMX_X2, false, 32, 0, 320)->launch == launch_resnet<bf16_t, 32, 2, 4, 2, false> && resnet_select(MMX_X2, false, 32, 0, 256)->launch == launch_resnet<bf16_t, 32, 4, 8, 2, false>);
+static_assert(resnet_select(MMX_X2, false, 32, 16 * 4, 256)->launch == launch_resnet<bf16_t, 32, 4, 4, 2, false> && resnet_select(MMX_X2, false, 16, 0, 512)->launch == launch_resnet<bf16_t, 16, 4, 4, 2, false>);
+static_assert(resnet_select(MMX_X2, true, 32, 0, 320)->launch == launch_resnet<bf16_t, 32, 2, 4, 2, true> && resnet_select(MMX_X2, true, 32, 0, 256)->launch == launch_resnet<bf16_t, 32, 4, 8, 2, true>);
+static_assert(resnet_select(MMX_X2, true, 32, 16 * 4, 256)->launch == launch_resnet<bf16_t, 32, 4, 4, 2, true> && resnet_select(MMX_F32, false, 16, 0, 256)->launch == launch_resnet<float, 16, 8, 4, 1, false>);
+
+// ---- dac_ru
+template <int C, int BM, int WR, int WC, int NS, int PF, bool WP>
+int launch_dac_ru(const MmxDacRuParams& p, hipStream_t stream) {
+    const size_t lds = dac_ru_lds(C, BM, NS, p.dil);
+    MMX_CHECK_ARG(lds <= LDS_MAX);
+    MMX_LDS_OPT_IN((dac_ru_kernel<C, BM, WR, WC, NS, PF, WP>), lds);
+    hipLaunchKernelGGL((dac_ru_kernel<C, BM, WR, WC, NS, PF, WP>), dim3((p.T + BM - 1) / BM, p.B), dim3(256), lds, stream, p);
+    MMX_LAUNCH_CHECK();
+    return MMX_OK;
+}
+using DacRuForm = Form<MmxDacRuParams>;
+template <int C, int BM, int WR, int WC, int NS, int PF, bool WP = false>
+constexpr DacRuForm dac_ru_form() { return {NS == 2 ? MMX_X2 : MMX_BF16, WP, BM, 0, 0, 0, C, launch_dac_ru<C, BM, WR, WC, NS, PF, WP>}; }
+constexpr DacRuForm DAC_RU_FORMS[] = {
+    dac_ru_form<48, 256, 4, 1, 1, 2>(), dac_ru_form<48, 128, 4, 1, 1, 2>(), dac_ru_form<48, 64, 4, 1, 1, 2>(),          // bf16 build
+    dac_ru_form<96, 256, 2, 2, 1, 3>(), dac_ru_form<96, 128, 2, 2, 1, 3>(), dac_ru_form<96, 64, 2, 2, 1, 3>(),
+    dac_ru_form<192, 128, 1, 4, 1, 2>(), dac_ru_form<192, 64, 1, 4, 1, 2>(), dac_ru_form<192, 32, 1, 4, 1, 2>(),
+    dac_ru_form<48, 128, 4, 1, 2, 2>(), dac_ru_form<48, 64, 4, 1, 2, 2>(),                                              // split build
+    dac_ru_form<96, 128, 2, 2, 2, 3>(), dac_ru_form<96, 64, 2, 2, 2, 3>(), dac_ru_form<96, 32, 2, 2, 2, 3>(),
+    dac_ru_form<192, 32, 1, 4, 2, 2>(), dac_ru_form<192, 16, 1, 4, 2, 2>(),
+    dac_ru_form<48, 64, 4, 1, 2, 2, true>(), dac_ru_form<96, 128, 2, 2, 2, 3, true>(), dac_ru_form<96, 64, 2, 2, 2, 3, true>(),   // weight planes
+    dac_ru_form<192, 32, 1, 4, 2, 2, true>(),
+};
+// dtype: MMX_X2 for MMX_X2W, which sets wp (w7 / w1 are [hi pack | lo pack])
+constexpr const DacRuForm* dac_ru_select(int dtype, bool wp, int bm, int C, int dil) {
+    // tile heights: default = the measured best of tools/dac_lab.py for (C, dtype); smaller tiles let two workgroups share a
+    // CU (LDS, 256 registers), which overlaps one's load / epilogue phases with the other's MFMA stages
+    const int dflt = dtype == MMX_BF16 ? (C == 48 ? 128 : C == 96 ? 256 : dil > 3 ? 32 : 64)
+                   : dtype == MMX_X2   ? (C == 48 ? 64 : C == 96 ? (dil > 3 ? 128 : 64) : 32) : 0;
+    if (wp && bm != 0 && bm != dflt) return nullptr;   // weight planes: the split build's default tile per stage, and no other
+    return find_form(DAC_RU_FORMS, dtype, wp, bm ? bm : dflt, 0, 0, 0, C);
+}
+// the defaults (bm = 0) per (dtype, C, dil); the decoder's dilations are 1 / 3 / 9
+static_assert(dac_ru_select(MMX_BF16, false, 0, 48, 9)->launch == launch_dac_ru<48, 128, 4, 1, 1, 2, false> && dac_ru_select(MMX_BF16, false, 0, 96, 9)->launch == launch_dac_ru<96, 256, 2, 2, 1, 3, false>);
+static_assert(dac_ru_select(MMX_BF16, false, 0, 192, 3)->launch == launch_dac_ru<192, 64, 1, 4, 1, 2, false> && dac_ru_select(MMX_BF16, false, 0, 192, 9)->launch == launch_dac_ru<192, 32, 1, 4, 1, 2, false>);
+static_assert(dac_ru_select(MMX_X2, false, 0, 48, 9)->launch == launch_dac_ru<48, 64, 4, 1, 2, 2, false> && dac_ru_select(MMX_X2, false, 0, 192, 9)->launch == launch_dac_ru<192, 32, 1, 4, 2, 2, false>);
+static_assert(dac_ru_select(MMX_X2, false, 0, 96, 3)->launch == launch_dac_ru<96, 64, 2, 2, 2, 3, false> && dac_ru_select(MMX_X2, false, 0, 96, 9)->launch == launch_dac_ru<96, 128, 2, 2, 2, 3, false>);
+static_assert(dac_ru_select(MMX_X2, true, 0, 48, 9)->launch == launch_dac_ru<48, 64, 4, 1, 2, 2, true> && dac_ru_select(MMX_X2, true, 0, 192, 9)->launch == launch_dac_ru<192, 32, 1, 4, 2, 2, true>);
+static_assert(dac_ru_select(MMX_X2, true, 0, 96, 3)->launch == launch_dac_ru<96, 64, 2, 2, 2, 3, true> && dac_ru_select(MMX_X2, true, 0, 96, 9)->launch == launch_dac_ru<96, 128, 2, 2, 2, 3, true>);
+
 }  // namespace
 
 #if MMX_LAB
@@ -1287,8 +1470,8 @@ extern "C" int mmx_lab_tail_stamps(void* buf) {
 }
 #endif
 
-// cfg = pf + 16 * waves: pf = k-steps of weight fragments a wave keeps in flight (2 / 4 / 8, 0 = default for the tile),
-// waves = 4 or 8 per workgroup (0 = default)
+// cfg = pf + 16 * waves (+ 512 * narrow): pf = k-steps of weight fragments a wave keeps in flight (2 / 4 / 8, 0 = default for the tile),
+// waves = 4 or 8 per workgroup (0 = default); the forms and the defaults: TAIL_FORMS / tail_select
 extern "C" int mmx_est_tail(const MmxEstTailParams* pp, int dtype, int bm, int cfg, hipStream_t stream) {
     MMX_CHECK_ARG(pp != nullptr);
     const MmxEstTailParams& p = *pp;
@@ -1300,75 +1483,8 @@ extern "C" int mmx_est_tail(const MmxEstTailParams* pp, int dtype, int bm, int c
     MMX_CHECK_ARG(((uintptr_t)p.ao % 16) == 0 && ((uintptr_t)p.x % 16) == 0);
     MMX_CHECK_ARG(!p.act_out || (p.act_ld % (dtype == MMX_X2 ? 4 : 8) == 0 && p.act_bs % (dtype == MMX_X2 ? 4 : 8) == 0 && ((uintptr_t)p.act_out % 16) == 0));
     if (int rc = check_next(p.next, dtype, p.T)) return rc;
-    const int nw = (cfg >> 4) & 15, occ2 = (cfg >> 8) & 1;
-#define TAILT(TT, BM, PF, NW, NS, OCC, PW, ...)                                                           \
-    do {                                                                                                   \
-        const size_t lds = tail_lds<TT, BM, NW, NS>();                                                     \
-        MMX_CHECK_ARG(lds * OCC <= 160 * 1024);                                                            \
-        MMX_LDS_OPT_IN((est_tail_kernel<TT, BM, PF, NW, NS, OCC, PW __VA_OPT__(,) __VA_ARGS__>), lds);     \
-        hipLaunchKernelGGL((est_tail_kernel<TT, BM, PF, NW, NS, OCC, PW __VA_OPT__(,) __VA_ARGS__>), dim3((p.T - p.t_begin + BM - 1) / BM, p.B), dim3(64 * NW), lds, stream, p); \
-    } while (0)
-#define TAILP(TT, BM, PF, NW, NS, OCC, PW) TAILT(TT, BM, PF, NW, NS, OCC, PW)
-#define TAILO(TT, BM, PF, NW, NS, OCC) TAILP(TT, BM, PF, NW, NS, OCC, 4)
-#define TAILN(TT, BM, PF, NW, NS) TAILO(TT, BM, PF, NW, NS, 1)
-#define TAIL(TT, BM, PF, NW) TAILN(TT, BM, PF, NW, 1)
-    int narrow = (cfg >> 9) & 1;
-    int pf = cfg & 15;
-    if (wplanes) {                                     // weight planes: the split build's default tiles
-        if (bm == 64) TAILT(bf16_t, 64, 2, 8, 2, 1, 2, true);
-        else if (bm == 32) TAILT(bf16_t, 32, 2, 8, 2, 1, 4, true);
-        else if (bm == 16) TAILT(bf16_t, 16, 4, 8, 2, 1, 4, true);
-        else return MMX_EARG;
-        MMX_LAUNCH_CHECK();
-        return MMX_OK;
-    }
-    if ((cfg >> 10) & 1) return MMX_EARG;              // (two row tiles per workgroup: removed, see est_tail_kernel)
-    // library defaults of the bf16 build (cfg = 0): the narrow-pass 8-wave kernels for the 64- and 32-row tiles (measured per
-    // launch at 10 000 rows: 51.1 us against 58.7 us with 4 waves x 64-column passes; 32 rows, 4 000 rows: 31.8 against 33.0)
-    if (cfg == 0 && dtype == MMX_BF16 && (bm == 64 || bm == 32)) { narrow = 1; pf = bm == 64 ? 2 : 8; }
-    // split build, 64 rows: two planes of 64 rows fit with the attention tile in K halves and 256-wide FF chunks (est_tail_tile, HK)
-    if (dtype == MMX_X2 && bm == 64) { narrow = 1; if (pf != 4) pf = 2; }
-    if (occ2) return MMX_EARG;                         // (two 4-wave workgroups per CU: measured slower everywhere, spilled; removed)
-    if (narrow) {                                      // 8 waves, 32-column passes (PW = 2)
-        if (dtype == MMX_BF16 && bm == 64) TAILP(bf16_t, 64, 2, 8, 1, 1, 2);
-        else if (dtype == MMX_BF16 && bm == 32) { if (pf == 8) TAILP(bf16_t, 32, 8, 8, 1, 1, 2); else TAILP(bf16_t, 32, 4, 8, 1, 1, 2); }
-        else if (dtype == MMX_X2 && bm == 32) { if (pf == 2) TAILP(bf16_t, 32, 2, 8, 2, 1, 2); else TAILP(bf16_t, 32, 4, 8, 2, 1, 2); }
-        else if (dtype == MMX_X2 && bm == 64) { if (pf == 4) TAILP(bf16_t, 64, 4, 8, 2, 1, 2); else TAILP(bf16_t, 64, 2, 8, 2, 1, 2); }
-        else return MMX_EARG;
-    } else if (dtype == MMX_X2) {
-        // split build: two bf16 planes per LDS tile, so the largest tile is 32 rows (137 KB with 8 waves)
-        // (a ring 4 k-steps deep measured no faster: 35.7 / 38.5 / 54.6 us at 32 / 128 / 256 workgroups against 37.4 / 40.4 / 55.2 -
-        // the stages are bound by the CU's L2 read rate, not by the latency of the loads in flight: profiles/r04_tail_lab_x.txt)
-        if (bm == 32) { if (nw == 4) TAILN(bf16_t, 32, 4, 4, 2); else TAILN(bf16_t, 32, 2, 8, 2); }
-        // (16 rows: 8 waves by default like the taller tiles - every split tile then sums its LayerNorms alike and an utterance's bits do
-        // not depend on the tile height its flow group was given; 4 waves with an explicit cfg)
-        else if (bm == 16) { if (nw == 4) TAILN(bf16_t, 16, 8, 4, 2); else TAILN(bf16_t, 16, 4, 8, 2); }
-        else return MMX_EARG;
-    } else if (dtype == MMX_BF16) {
-        if (bm == 64) {                                // (reached with an explicit cfg only: the round-2 / round-3 forms, tools/tail_lab.py)
-            if (nw == 0 || nw == 4) { if (pf == 4) TAIL(bf16_t, 64, 4, 4); else TAIL(bf16_t, 64, 2, 4); }
-            else return MMX_EARG;
-        } else if (bm == 32) {
-            if (nw == 8 || nw == 0) { if (pf == 4) TAIL(bf16_t, 32, 4, 8); else TAIL(bf16_t, 32, 2, 8); }
-            else if (nw == 4) { if (pf == 2) TAIL(bf16_t, 32, 2, 4); else TAIL(bf16_t, 32, 4, 4); }
-            else return MMX_EARG;
-        } else if (bm == 16) {
-            if (nw == 8) TAIL(bf16_t, 16, 4, 8);
-            else if (nw == 0 || nw == 4) TAIL(bf16_t, 16, 8, 4);
-            else return MMX_EARG;
-        } else return MMX_EARG;
-    } else if (dtype == MMX_F32) {
-        if (bm == 32 && (nw == 0 || nw == 4)) TAIL(float, 32, 4, 4);
-        else if (bm == 16 && (nw == 0 || nw == 4)) TAIL(float, 16, 8, 4);
-        else return MMX_EARG;
-    } else return MMX_EARG;
-#undef TAIL
-#undef TAILN
-#undef TAILO
-#undef TAILP
-#undef TAILT
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    const TailForm* form = tail_select(dtype, wplanes, bm, cfg);
+    return form ? form->launch(p, stream) : MMX_EARG;
 }
 
 extern "C" int mmx_est_resnet(const MmxEstResnetParams* pp, int dtype, int bm, int cfg, hipStream_t stream) {
@@ -1382,74 +1498,8 @@ extern "C" int mmx_est_resnet(const MmxEstResnetParams* pp, int dtype, int bm, i
     MMX_CHECK_ARG(p.lda % (dtype == MMX_X2 ? 4 : 8) == 0 && p.a_bs % (dtype == MMX_X2 ? 4 : 8) == 0);
     MMX_CHECK_ARG(((uintptr_t)p.a_in % 16) == 0 && ((uintptr_t)p.x % 16) == 0 && p.x_bs % 4 == 0 && p.tv_bs % 4 == 0 && ((uintptr_t)p.tv % 16) == 0);
     if (int rc = check_next(p.next, dtype, p.T)) return rc;
-    const int pf_req = cfg & 15, nw = cfg >> 4;
-#define RESNN(TT, BM, PF, NW, NS, ...)                                                                    \
-    do {                                                                                                   \
-        const size_t lds = resnet_lds<TT, BM, NW, NS>(p.cin);                                              \
-        MMX_CHECK_ARG(lds <= 160 * 1024);                                                                  \
-        MMX_LDS_OPT_IN((est_resnet_kernel<TT, BM, PF, NW, NS __VA_OPT__(,) __VA_ARGS__>), lds);            \
-        hipLaunchKernelGGL((est_resnet_kernel<TT, BM, PF, NW, NS __VA_OPT__(,) __VA_ARGS__>), dim3((p.T - p.t_begin + BM - 1) / BM, p.B), dim3(64 * NW), lds, stream, p); \
-    } while (0)
-#define RESN(TT, BM, PF, NW) RESNN(TT, BM, PF, NW, 1)
-    // ring depth: the deepest of 8 / 4 / 2 the tile height wants that divides every stage's k-step count
-    // (conv k3 over cin, conv k3 over 256, 1x1 over cin, Q/K/V over 256); cin = 320 allows 2 (bf16) / 4 (fp32) only
-    const int kb = dtype == MMX_F32 ? 16 : 32;
-    if (dtype == MMX_X2) {
-        // split build (two bf16 planes per LDS tile): 32-row tiles while the input tile leaves room (cin <= 320: 150 KB with
-        // 4 waves), 16 rows for the 512-channel input of the up block; ring depth as the bf16 build's rule below
-        int pfx = pf_req > 0 ? pf_req : 4;
-        while (pfx > 2 && ((3 * p.cin / kb) % pfx || (p.cin / kb) % pfx || (256 / kb) % pfx)) pfx /= 2;
-        MMX_CHECK_ARG((p.cin / kb) % 2 == 0);
-        if (bm == 32) {
-            MMX_CHECK_ARG((resnet_lds<bf16_t, 32, 4, 2>(p.cin)) <= 160 * 1024);
-            if (wplanes && nw != 4 && (resnet_lds<bf16_t, 32, 8, 2>(p.cin)) <= 160 * 1024) { if (pfx >= 4) RESNN(bf16_t, 32, 4, 8, 2, true); else RESNN(bf16_t, 32, 2, 8, 2, true); }
-            else if (wplanes) { if (pfx >= 4) RESNN(bf16_t, 32, 4, 4, 2, true); else RESNN(bf16_t, 32, 2, 4, 2, true); }
-            // 8 waves (two per SIMD: a wave alone on its SIMD issues vector instructions at half the SIMD's rate, and the epilogues
-            // here are vector work) where the per-wave patches still fit beside the two-plane tiles: cin = 256, the twelve mid blocks
-            else if (nw != 4 && (resnet_lds<bf16_t, 32, 8, 2>(p.cin)) <= 160 * 1024) { if (pfx >= 4) RESNN(bf16_t, 32, 4, 8, 2); else RESNN(bf16_t, 32, 2, 8, 2); }
-            else if (pfx >= 4) RESNN(bf16_t, 32, 4, 4, 2); else RESNN(bf16_t, 32, 2, 4, 2);
-        } else if (bm == 16) {
-            // (8 waves under the same condition as the 32-row tile: both tile heights then sum every LayerNorm alike - bit-identical)
-            if (nw != 4 && (resnet_lds<bf16_t, 32, 8, 2>(p.cin)) <= 160 * 1024) {
-                if (wplanes) { if (pfx >= 4) RESNN(bf16_t, 16, 4, 8, 2, true); else RESNN(bf16_t, 16, 2, 8, 2, true); }
-                else if (pfx >= 4) RESNN(bf16_t, 16, 4, 8, 2); else RESNN(bf16_t, 16, 2, 8, 2);
-            }
-            else if (wplanes) { if (pfx >= 4) RESNN(bf16_t, 16, 4, 4, 2, true); else RESNN(bf16_t, 16, 2, 4, 2, true); }
-            else if (pfx >= 4) RESNN(bf16_t, 16, 4, 4, 2); else RESNN(bf16_t, 16, 2, 4, 2);
-        } else return MMX_EARG;
-        MMX_LAUNCH_CHECK();
-        return MMX_OK;
-    }
-    // 8 waves (two per SIMD) measured faster for the 64-row ResNet tile (50.6 vs 59.7 us at 14 336 rows); they need 17 KB
-    // more LDS for the per-wave patches, which the 512-channel input tile (up block) does not leave
-    // (and for the smaller tiles: 31.7 vs 36.2 us at 32 rows, 26.9 vs 29.0 us at 16 rows)
-    const size_t lds8 = bm == 64 ? resnet_lds<bf16_t, 64, 8>(p.cin) : (bm == 32 ? resnet_lds<bf16_t, 32, 8>(p.cin) : resnet_lds<bf16_t, 16, 8>(p.cin));
-    const bool w8 = dtype == MMX_BF16 && (nw == 8 || (nw == 0 && lds8 <= 160 * 1024));
-    const int want = pf_req > 0 ? pf_req : (w8 ? (bm == 64 ? 2 : 4) : (bm == 16 ? 8 : 4));
-    MMX_CHECK_ARG(want == 2 || want == 4 || want == 8);
-    int pf = want;
-    while (pf > 2 && ((3 * p.cin / kb) % pf || (p.cin / kb) % pf || (256 / kb) % pf)) pf /= 2;
-    MMX_CHECK_ARG((p.cin / kb) % 2 == 0 && (nw == 0 || nw == 4 || nw == 8));
-    if (dtype == MMX_BF16) {
-        if (w8) {
-            if (bm == 64) RESN(bf16_t, 64, 2, 8);
-            else if (bm == 32) { if (pf >= 4) RESN(bf16_t, 32, 4, 8); else RESN(bf16_t, 32, 2, 8); }
-            else if (bm == 16) { if (pf >= 4) RESN(bf16_t, 16, 4, 8); else RESN(bf16_t, 16, 2, 8); }
-            else return MMX_EARG;
-        } else {
-            if (bm == 64) { if (pf >= 4) RESN(bf16_t, 64, 4, 4); else RESN(bf16_t, 64, 2, 4); }
-            else if (bm == 32) { if (pf >= 4) RESN(bf16_t, 32, 4, 4); else RESN(bf16_t, 32, 2, 4); }
-            else if (bm == 16) { if (pf == 8) RESN(bf16_t, 16, 8, 4); else if (pf == 4) RESN(bf16_t, 16, 4, 4); else RESN(bf16_t, 16, 2, 4); }
-            else return MMX_EARG;
-        }
-    } else if (dtype == MMX_F32) {
-        if (bm == 16 && (nw == 0 || nw == 4)) { if (pf == 8) RESN(float, 16, 8, 4); else if (pf == 4) RESN(float, 16, 4, 4); else RESN(float, 16, 2, 4); }
-        else return MMX_EARG;
-    } else return MMX_EARG;
-#undef RESN
-#undef RESNN
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    const ResnetForm* form = resnet_select(dtype, wplanes, bm, cfg, p.cin);
+    return form ? form->launch(p, stream) : MMX_EARG;
 }
 
 extern "C" int mmx_dac_ru(const MmxDacRuParams* pp, int dtype, int bm, hipStream_t stream) {
@@ -1460,35 +1510,6 @@ extern "C" int mmx_dac_ru(const MmxDacRuParams* pp, int dtype, int bm, hipStream
     MMX_CHECK_ARG(((uintptr_t)p.x % 16) == 0 && ((uintptr_t)p.x_out % 16) == 0 && ((uintptr_t)p.act_out % 16) == 0 && ((uintptr_t)p.a0 % 16) == 0);
     MMX_CHECK_ARG(!p.act_out || p.alpha_next);
     const bool wplanes = dtype == MMX_X2W;             // w7 / w1 are [hi pack | lo pack]
-    if (wplanes) dtype = MMX_X2;
-    MMX_CHECK_ARG(dtype == MMX_BF16 || dtype == MMX_X2);
-#define DACRU(C_, BM_, WR_, WC_, NS_, PF_, ...)                                                            \
-    do {                                                                                                   \
-        const size_t lds = dac_ru_lds<C_, BM_, NS_>(p.dil);                                                \
-        MMX_CHECK_ARG(lds <= 160 * 1024);                                                                  \
-        MMX_LDS_OPT_IN((dac_ru_kernel<C_, BM_, WR_, WC_, NS_, PF_ __VA_OPT__(,) __VA_ARGS__>), lds);       \
-        hipLaunchKernelGGL((dac_ru_kernel<C_, BM_, WR_, WC_, NS_, PF_ __VA_OPT__(,) __VA_ARGS__>), dim3((p.T + BM_ - 1) / BM_, p.B), dim3(256), lds, stream, p); \
-    } while (0)
-    if (wplanes) {                                     // weight planes: the split build's default tile per stage, and no other
-        if (bm != 0 && bm != (p.C == 48 ? 64 : p.C == 96 ? (p.dil > 3 ? 128 : 64) : 32)) return MMX_EARG;
-        if (p.C == 48) DACRU(48, 64, 4, 1, 2, 2, true);
-        else if (p.C == 96) { if (p.dil > 3) DACRU(96, 128, 2, 2, 2, 3, true); else DACRU(96, 64, 2, 2, 2, 3, true); }
-        else DACRU(192, 32, 1, 4, 2, 2, true);
-        MMX_LAUNCH_CHECK();
-        return MMX_OK;
-    }
-    // tile heights: default = the measured best of tools/dac_lab.py for (C, dtype); smaller tiles let two workgroups share a
-    // CU (LDS, 256 registers), which overlaps one's load / epilogue phases with the other's MFMA stages
-    if (dtype == MMX_BF16) {
-        if (p.C == 48) { if (bm == 256) DACRU(48, 256, 4, 1, 1, 2); else if (bm == 0 || bm == 128) DACRU(48, 128, 4, 1, 1, 2); else if (bm == 64) DACRU(48, 64, 4, 1, 1, 2); else return MMX_EARG; }
-        else if (p.C == 96) { if (bm == 0 || bm == 256) DACRU(96, 256, 2, 2, 1, 3); else if (bm == 128) DACRU(96, 128, 2, 2, 1, 3); else if (bm == 64) DACRU(96, 64, 2, 2, 1, 3); else return MMX_EARG; }
-        else { if (bm == 0) bm = p.dil > 3 ? 32 : 64; if (bm == 128) DACRU(192, 128, 1, 4, 1, 2); else if (bm == 64) DACRU(192, 64, 1, 4, 1, 2); else if (bm == 32) DACRU(192, 32, 1, 4, 1, 2); else return MMX_EARG; }
-    } else {
-        if (p.C == 48) { if (bm == 128) DACRU(48, 128, 4, 1, 2, 2); else if (bm == 0 || bm == 64) DACRU(48, 64, 4, 1, 2, 2); else return MMX_EARG; }
-        else if (p.C == 96) { if (bm == 0) bm = p.dil > 3 ? 128 : 64; if (bm == 128) DACRU(96, 128, 2, 2, 2, 3); else if (bm == 64) DACRU(96, 64, 2, 2, 2, 3); else if (bm == 32) DACRU(96, 32, 2, 2, 2, 3); else return MMX_EARG; }
-        else { if (bm == 0 || bm == 32) DACRU(192, 32, 1, 4, 2, 2); else if (bm == 16) DACRU(192, 16, 1, 4, 2, 2); else return MMX_EARG; }
-    }
-#undef DACRU
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    const DacRuForm* form = dac_ru_select(wplanes ? MMX_X2 : dtype, wplanes, bm, p.C, p.dil);
+    return form ? form->launch(p, stream) : MMX_EARG;
 }

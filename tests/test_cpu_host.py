@@ -321,3 +321,23 @@ def test_flow_tile_rule_of_the_split_build():
     # the model itself: full rounds of 256 workgroups, then the remainder; a fuller chip streams the shared weights slower
     assert FlowEngine._launch_us(64, 256, True) > FlowEngine._launch_us(64, 16, True) > FlowEngine._launch_us(32, 16, True)
     assert abs(FlowEngine._launch_us(32, 512, True) - 2 * FlowEngine._launch_us(32, 256, True)) < 1e-9
+
+
+def test_gated_fused_forms_are_the_pinned_defaults():
+    """tools/check_resources.py gates the est_tail / est_resnet kernels the defaults launch; which those are is pinned by the
+    static_asserts under tail_select / resnet_select in csrc/fused.hip.  Every gated form is one of the pinned ones."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("check_resources", os.path.join(ROOT, "tools", "check_resources.py"))
+    cr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cr)
+    pinned = set()
+    for line in open(os.path.join(ROOT, "minimax-speech_amd", "csrc", "fused.hip")):
+        if line.startswith("static_assert("):
+            for fam, args in re.findall(r"launch_(tail|resnet)<([^>]*)>", line):
+                a = [x.strip() for x in args.split(",")]
+                a[0] = {"bf16_t": "unsigned short", "float": "float"}[a[0]]
+                if fam == "tail":
+                    a.insert(5, "1")                      # est_tail_kernel's OCC, which launch_tail fixes at 1
+                pinned.add(f"est_{fam}_kernel<{', '.join(a)}>")
+    gated = [g for g in cr.GATED if g.startswith(("est_tail_kernel<", "est_resnet_kernel<"))]
+    assert len(gated) == 17 and [g for g in gated if g not in pinned] == []

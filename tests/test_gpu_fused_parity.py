@@ -402,12 +402,12 @@ def judge(out, c, tb, T, what, group):
         assert_rows(out[k], r[:, tb:T], c["bound"], f"{what} {k}", group)
 
 
-# (dtype, form, bm, cfg): every instantiation mmx_est_tail dispatches to
+# (dtype, form, bm, cfg): every instantiation mmx_est_tail dispatches to (the rows of TAIL_FORMS in csrc/fused.hip)
 TAIL_VARIANTS = (
     [(0, None, bm, {}) for bm in (16, 32)]
     + [(1, None, bm, {}) for bm in (16, 32, 64)]
     + [(1, None, 64, dict(waves=4, pf=2)), (1, None, 64, dict(waves=4, pf=4)), (1, None, 32, dict(waves=4, pf=4)), (1, None, 32, dict(waves=8, pf=2)),
-       (1, None, 16, dict(waves=8)), (1, None, 32, dict(narrow=True, pf=4))]
+       (1, None, 16, dict(waves=8)), (1, None, 32, dict(narrow=True, pf=4)), (1, None, 32, dict(waves=4, pf=2)), (1, None, 32, dict(waves=8, pf=4))]
     + [(X2, None, 32, {}), (X2, None, 32, dict(waves=4)), (X2, None, 16, {}), (X2, None, 16, dict(waves=4)), (X2, None, 32, dict(narrow=True, pf=2)),
        (X2, None, 32, dict(narrow=True, pf=4)), (X2, None, 64, {}), (X2, None, 64, dict(pf=4))]
     + [(X2W, None, bm, {}) for bm in (16, 32, 64)]

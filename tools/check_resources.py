@@ -12,7 +12,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "minimax-speech_amd", "csrc")
 FLAGS = "-O3 --offload-arch=gfx950 -fPIC -std=c++20 -Wno-unused-result -Wno-pass-failed -Rpass-analysis=kernel-resource-usage".split()
-# demangled-name prefixes of the kernels the default configurations launch (mmx/flow.py, mmx/llm.py, mmx/dac.py tile rules)
+# demangled-name prefixes of the kernels the default configurations launch (mmx/flow.py, mmx/llm.py, mmx/dac.py tile rules); the
+# est_tail / est_resnet forms are those the static_asserts under tail_select / resnet_select in csrc/fused.hip pin to the defaults
 GATED = [
     "est_tail_kernel<unsigned short, 64, 2, 8, 1, 1, 2, false>",      # bf16 build, 64-row tiles
     "est_tail_kernel<unsigned short, 32, 8, 8, 1, 1, 2, false>",      # bf16 build, 32-row tiles

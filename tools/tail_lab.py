@@ -40,7 +40,7 @@ def run(n, T, bm, waves, pf):
         w, wn = blocks[i % len(blocks)], blocks[(i + 1) % len(blocks)]
         nxt = ops.est_next(wqkv=wn["wqkv_p"], n1g=wn["n1g"], n1b=wn["n1b"], q_out=qk, ldq=ldq, q_bs=T * ldq, vt_out=vt, ldvt=Tp,
                            vt_bs=vt_bs)
-        ops.est_tail(ao, x, w, B=B, T=T, dtype=dt, bm=bm, nxt=nxt, waves=waves % 100, pf=pf, occ2=100 <= waves < 200, narrow=200 <= waves < 300)
+        ops.est_tail(ao, x, w, B=B, T=T, dtype=dt, bm=bm, nxt=nxt, waves=waves % 100, pf=pf, narrow=waves >= 200)
 
     return _event_time_graph(one, 2 * len(blocks))
 
@@ -87,7 +87,7 @@ def stamps(n=5, T=1000, bm=64, waves=4, pf=2):
                            vt_bs=vt_bs)
         if i == 5:
             assert lib.mmx_lab_tail_stamps(C.c_void_p(buf.data_ptr())) == 0
-        ops.est_tail(ao, x, w, B=B, T=T, dtype=dt, bm=bm, nxt=nxt, waves=waves % 100, pf=pf, occ2=100 <= waves < 200, narrow=waves >= 200)
+        ops.est_tail(ao, x, w, B=B, T=T, dtype=dt, bm=bm, nxt=nxt, waves=waves % 100, pf=pf, narrow=waves >= 200)
     torch.cuda.synchronize()
     assert lib.mmx_lab_tail_stamps(C.c_void_p(0)) == 0
     s = buf.cpu().reshape(nwg, nw, 64).double()
