@@ -554,6 +554,32 @@ int mmx_s3_rope_fsmn(float* qkv, int64_t ldqkv, int64_t qkv_bs, int B, int T, in
 int mmx_fsq_encode(const float* x, int64_t ldx, int64_t x_bs, int B, int T, int C, const float* W, const float* bias,
                    const int32_t* lens, int32_t* ids, int64_t ld_ids, float* pre, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * mmx_resample_sinc: sample-rate conversion of a ragged batch of mono clips in one launch, the polyphase windowed-sinc FIR that
+ * torchaudio documents as `sinc_interp_hann` (what cosyvoice/utils/file_utils.py:44-50 and cli/frontend.py:157-162 call).
+ *   orig -> neu: the two rates divided by their gcd (coprime, different).  With base = min(orig, neu) * rolloff and
+ *   width = ceil(lpw * orig / base), output j = f * neu + p (frame f, phase p) of a clip x[0 .. len) is
+ *       y[j] = sum_k h[p][k] * x[f * orig + k - width],   k in [0, 2 * width + orig),   x = 0 outside [0, len),
+ *       h[p][k] = fp32((base / orig) * sinc(pi t) * cos^2(pi t / (2 lpw))),  t = base * ((k - width) / orig - p / neu) in float64,
+ *   and a clip has ceil(neu * len / orig) outputs (64-bit arithmetic).  Taps with |t| >= lpw are exactly 0 in fp32, so the bank
+ *   arrives packed (mmx/resample.py builds it):
+ *   first int32 [neu]: the dense index k of a phase's first live tap;  count int32 [neu]: its live taps (<= cmax <= 2 * width);
+ *   taps  fp32 [cmax][neu], tap-major: taps[c][p] = h[p][first[p] + c], zero beyond count[p].
+ *   wave  fp32 [B][w_bs >= L];  lens int32 [B] or NULL (= L): valid samples per clip, each >= 1, h_lens the same values in HOST
+ *         memory (given exactly when lens is); samples at or beyond lens[b] are never read.
+ *   out   fp32 [B][o_bs >= out_cols]: columns [0, ceil(neu * lens[b] / orig)) hold the result, the columns from there to out_cols
+ *         are written as 0, nothing else is written.
+ * A workgroup owns MMX_RESAMPLE_NOUT consecutive outputs of one clip and holds the packed bank and the input span under them in
+ * LDS.  Every output is one thread's fp32 sum over its live taps in ascending order (fmaf), so a clip's bits do not depend on the
+ * batch, on its row or on the workgroup.
+ * MMX_EARG: rates that are equal or not coprime, a length outside [1, L], out_cols smaller than a clip's output count, or a rate
+ *   pair whose packed bank plus input span, (cmax * neu + ceil((MMX_RESAMPLE_NOUT - 1) * orig / neu) + 2 * width + 2) * 4 bytes,
+ *   exceeds 64 KB of LDS (16001 -> 16000 does; every pair of the usual audio rates is far below).  Nothing is launched then. */
+#define MMX_RESAMPLE_NOUT 1024
+int mmx_resample_sinc(const float* wave, int64_t w_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, int orig, int neu,
+                      int width, const float* taps, const int32_t* first, const int32_t* count, int cmax, float* out,
+                      int64_t o_bs, int out_cols, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

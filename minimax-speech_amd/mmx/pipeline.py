@@ -162,11 +162,13 @@ class TtsEngine:
         return self._latents2wav(self.flow.inference_time_major(token, prompt_token, prompt_feat, embedding, streaming, finalize))
 
     @torch.no_grad()
-    def reference_embedding(self, reference_audio, sample_rate=24000, cache=None) -> torch.Tensor:
+    def reference_embedding(self, reference_audio, sample_rate=24000, cache=None, resample=False) -> torch.Tensor:
         """A reference recording (a mono clip [n] / [1, n] on the device at `sample_rate`, or a list of clips of one speaker)
         -> the speaker embedding [1, 192] the flow is conditioned on: crop + peak gain, mmx_logmel, the learnable speaker
         encoder (SpeakerEncoderEngine.embed_audio).  Needs a flow checkpoint with `speaker_encoder.*` (use_speaker_encoder: True).
-        cache (a dict): one embedding per distinct clip object."""
+        cache (a dict): one embedding per distinct clip object.
+        resample=True: a recording at another rate is first brought to the mel tables' 24 kHz (mmx.resample, one launch for the
+        list) and embedded at that rate; the default crops in seconds of `sample_rate` and analyses the samples as they are."""
         if self.flow.spk_enc is None:
             raise RuntimeError("reference_audio needs the learnable speaker encoder: the flow state dict has no speaker_encoder.* "
                                "weights (speech/config.yaml use_speaker_encoder: True)")
@@ -174,6 +176,9 @@ class TtsEngine:
         if cache is not None and key in cache:
             return cache[key][1]
         clips = list(reference_audio) if isinstance(reference_audio, (list, tuple)) else [reference_audio]
+        if resample and sample_rate != SAMPLE_RATE:
+            from .resample import resample as resample_clips
+            clips, sample_rate = resample_clips(clips, sample_rate, SAMPLE_RATE), SAMPLE_RATE
         e = self.flow.spk_enc.embed_audio(clips, sample_rate)
         if cache is not None:
             cache[key] = (reference_audio, e)              # the clip is kept alive with its id
@@ -203,8 +208,8 @@ class TtsEngine:
 
     @torch.no_grad()
     def prompt_from_audio(self, wave16k, wave24k, prompt_text=None, noise=None, generator=None) -> dict:
-        """A zero-shot prompt from one recording given at both rates (mono [n] / [1, n] on the device; resampling stays with the
-        caller): frontend_zero_shot's speech part (cli/frontend.py:157-174).  wave16k -> speech tokens (the S3 tokenizer), wave24k
+        """A zero-shot prompt from one recording given at both rates (mono [n] / [1, n] on the device; prompt_from_clip
+        takes one clip and resamples it): frontend_zero_shot's speech part (cli/frontend.py:157-174).  wave16k -> speech tokens (the S3 tokenizer), wave24k
         -> prompt latents (DACVAE.encode's z, as processor.py:149-159 reads them; `noise` / `generator` as DacEncoderEngine.encode)
         and, where the flow has its speaker encoder, the embedding.  token_len = min(latent frames // 2, tokens); tokens are cut
         to token_len and the latents to 2 * token_len.  The result splats into tts / tts_stream:
@@ -222,6 +227,36 @@ class TtsEngine:
         if self.flow.spk_enc is not None:
             out["flow_embedding"] = self.reference_embedding(w24.reshape(-1), 24000)
         return out
+
+    @torch.no_grad()
+    def prompt_from_clip(self, wave, sample_rate, prompt_text=None, noise=None, generator=None, via_16k=True) -> dict:
+        """prompt_from_audio from ONE recording (mono [n] / [1, n]) at any rate: the two resamplings happen here, on the device
+        (mmx.resample.Resample).  via_16k=True is the reference's inference route: the file is brought to 16 kHz
+        (utils/file_utils.py:44-50 load_wav) and the features are taken from THAT clip brought to 24 kHz (cli/frontend.py:157-162);
+        via_16k=False brings the source to each rate directly, as the dataset tools do (tools/extract_speech_token.py:30,
+        tools/extract_embedding.py:30).  A rate that is already the wanted one is not resampled."""
+        from .resample import Resample
+        w = wave.to(self.dev, torch.float32).reshape(-1)
+        w16 = Resample(sample_rate, 16000)(w)
+        w24 = Resample(16000, SAMPLE_RATE)(w16) if via_16k else Resample(sample_rate, SAMPLE_RATE)(w)
+        return self.prompt_from_audio(w16, w24, prompt_text, noise, generator)
+
+    @torch.no_grad()
+    def voice_conversion(self, source_wave, source_rate, flow_prompt_speech_token, prompt_speech_feat, flow_embedding, speed=1.0,
+                         prompt_text=None, llm_prompt_speech_token=None) -> torch.Tensor:
+        """The words of `source_wave` (mono [n] / [1, n] at `source_rate`) in the prompt's voice, non-streaming: frontend_vc
+        (cli/frontend.py:205-213) and CosyVoice2.inference_vc (cli/cosyvoice.py:132-139 -> cli/model.py:331-335, the source's speech
+        tokens take the place of the LM's).  Source -> 16 kHz -> the S3 tokenizer -> token2wav with the prompt -> [1, 1, 2 * tokens *
+        hop].  Takes the splat of a prompt_from_clip / prompt_from_audio dict: eng.voice_conversion(src, rate, **prompt); the LM's
+        keys (prompt_text, llm_prompt_speech_token) are not used.  speed != 1: the latent frames are resampled linearly in time
+        to int(frames / speed) before the decoder (cli/model.py:312-315)."""
+        from .resample import Resample
+        w16 = Resample(source_rate, 16000)(source_wave.to(self.dev, torch.float32).reshape(-1))
+        tok = self.s3tok.tokenize([w16])[0].to(torch.long).reshape(1, -1)
+        if speed == 1.0:
+            return self.token2wav(tok, flow_prompt_speech_token, prompt_speech_feat, flow_embedding)
+        lat = self.flow.inference_time_major(tok, flow_prompt_speech_token, prompt_speech_feat, flow_embedding, False, True)
+        return self._latents2wav(ops.resample_linear(lat.float().t(), int(lat.shape[0] / speed)).t().contiguous())
 
     def _embedding_arg(self, flow_embedding, reference_audio, sample_rate):
         if (flow_embedding is None) == (reference_audio is None):
