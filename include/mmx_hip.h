@@ -336,6 +336,13 @@ int mmx_paged_attn(const void* q, int64_t ldq, int64_t q_bs, int B, int rows, in
 int mmx_decode_attn(const float* qkv, int64_t ldqkv, int B, int Hq, int Hkv, int D, const float* inv_freq,
                     const float* rope_tab, const int32_t* pos, void* kc, void* vc, const int32_t* block_table, int max_pages, int page,
                     float scale, void* out, int64_t ldo, int dtype, int out_packed, hipStream_t stream);
+/* mmx_decode_attn with the loop's `finished` flags (int32 [B], indexed like pos; NULL = mmx_decode_attn): the workgroups of a
+ * sequence whose flag is non-zero return at once - no K/V append, no cache read, its output row keeps what it held.  For decode
+ * loops that keep an ended sequence in its slot (pos frozen, its outputs ignored) until the slot is given to another one. */
+int mmx_decode_attn_fin(const float* qkv, int64_t ldqkv, int B, int Hq, int Hkv, int D, const float* inv_freq,
+                        const float* rope_tab, const int32_t* pos, const int32_t* finished, void* kc, void* vc,
+                        const int32_t* block_table, int max_pages, int page, float scale, void* out, int64_t ldo, int dtype,
+                        int out_packed, hipStream_t stream);
 /* SwiGLU for prefill: out = T(silu(gu[:, :I]) * gu[:, I:2I]) */
 int mmx_swiglu(const float* gu, int64_t ldgu, int rows, int I, void* out, int64_t ldo, int dtype, hipStream_t stream);
 

@@ -589,7 +589,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     const float* __restrict__ qkv, long ldqkv, int Hq, int Hkv, const float* __restrict__ inv_freq,
     const float* __restrict__ rope_tab, const int32_t* __restrict__ pos, T* __restrict__ kc, T* __restrict__ vc,
     const int32_t* __restrict__ block_table, int max_pages, int page, float scale, T* __restrict__ out, long ldo,
-    int nseq) {
+    int nseq, const int32_t* __restrict__ finished) {
     // Single pass ("flash decoding" inside one workgroup): thread = (key group kg of 32, channel chunk dc of 8).
     // For each of its keys a thread loads 16 B of the K row and 16 B of the V row (both in flight together), the 8
     // threads of a key reduce q.k with 3 xor-shuffles, every key group keeps its own running (max, sum, acc[8]) per head;
@@ -615,9 +615,13 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     if (kvg >= Hkv * nseq) return;                     // uniform: the grid is padded to a multiple of 8 pairs
     const int b = kvg / Hkv, hk = kvg % Hkv, sub = slot % nsub;
     const int h0 = hk * group + sub * HP, nh = min(HP, group - sub * HP);   // this workgroup's heads h0 .. h0 + nh - 1
+    // finished (or NULL): a sequence that has ended keeps its pos; nothing reads its output row and its cache row at pos was
+    // written the step it ended, so its workgroups leave here - the flag comes with pos, in the same round trip, and nothing
+    // of the block table, the cache or the output is touched before it is known
+    const int p = pos[b];
+    if (finished && finished[b]) return;               // uniform
     const int32_t* bt = block_table + (long)b * max_pages;
     for (int i = tid; i < max_pages; i += 256) bts[i] = bt[i];
-    const int p = pos[b];
     const float* src = qkv + (long)b * ldqkv;
     const float sc2 = scale * 1.44269504088896341f;
     if (tid < (HP + 1) * HALF) {
@@ -769,7 +773,8 @@ template <bool OPK, int G>
 __global__ __launch_bounds__(256) void decode_attn_gqa_kernel(
     const float* __restrict__ qkv, long ldqkv, int Hq, int Hkv, const float* __restrict__ inv_freq,
     const float* __restrict__ rope_tab, const int32_t* __restrict__ pos, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
-    const int32_t* __restrict__ block_table, int max_pages, float scale, bf16_t* __restrict__ out, long ldo, int nseq) {
+    const int32_t* __restrict__ block_table, int max_pages, float scale, bf16_t* __restrict__ out, long ldo, int nseq,
+    const int32_t* __restrict__ finished) {
     constexpr int D = 64, HALF = 32, PAGE = 16, NS = 8;             // NS page slots per wave and round
     static_assert(G <= 8, "one 8-float row of P per key");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -787,6 +792,7 @@ __global__ __launch_bounds__(256) void decode_attn_gqa_kernel(
     const int b = blockIdx.x / Hkv, hk = blockIdx.x % Hkv;
     const int32_t* bt = block_table + (long)b * max_pages;
     const int p = pos[b];
+    if (finished && finished[b]) return;                             // (uniform) an ended sequence: see decode_attn_kernel
     const int NT = p / PAGE + 1;                                     // pages that hold keys 0 .. p
     for (int i = tid; i < NT; i += 256) bts[i] = bt[i];
     for (int i = tid; i < 2 * 16 * D / 2; i += 256) reinterpret_cast<unsigned*>(qh)[i] = 0u;       // rows G..15 of qh / ql
@@ -975,9 +981,10 @@ __global__ __launch_bounds__(256) void decode_attn_gqa_kernel(
         out[OPK ? act_packed_index<bf16_t>(b, col, Hq * D) : (long)b * ldo + col] = f2bf(o / L);
     }
 }
-extern "C" int mmx_decode_attn(const float* qkv, int64_t ldqkv, int B, int Hq, int Hkv, int D, const float* inv_freq,
-                               const float* rope_tab, const int32_t* pos, void* kc, void* vc, const int32_t* block_table, int max_pages,
-                               int page, float scale, void* out, int64_t ldo, int dtype, int out_packed, hipStream_t stream) {
+extern "C" int mmx_decode_attn_fin(const float* qkv, int64_t ldqkv, int B, int Hq, int Hkv, int D, const float* inv_freq,
+                                   const float* rope_tab, const int32_t* pos, const int32_t* finished, void* kc, void* vc,
+                                   const int32_t* block_table, int max_pages, int page, float scale, void* out, int64_t ldo, int dtype,
+                                   int out_packed, hipStream_t stream) {
     dtype = MMX_ACT_DTYPE(dtype);
     MMX_CHECK_ARG(qkv && (inv_freq || rope_tab) && pos && kc && vc && block_table && out && B > 0 && D == 64 && Hq % Hkv == 0 && page > 0);
     MMX_CHECK_ARG(out_packed >= 0 && out_packed <= 31);
@@ -997,18 +1004,24 @@ extern "C" int mmx_decode_attn(const float* qkv, int64_t ldqkv, int B, int Hq, i
     size_t lds = ((size_t)hp * 64 + 2 * 64 + 2 * hp * 32 + (size_t)hp * 32 * 64 + (size_t)max_pages) * 4;
     MMX_CHECK_ARG(lds <= 64 * 1024);
     dim3 grid(8 * ((Hkv * B + 7) / 8) * nsub);
-#define DA(T, OM) do { if (one_head) hipLaunchKernelGGL((decode_attn_kernel<T, OM, 1>), grid, dim3(256), lds, stream, qkv, ldqkv, Hq, Hkv, inv_freq, rope_tab, pos, (T*)kc, (T*)vc, block_table, max_pages, page, scale, (T*)out, ldo, B); \
-                       else hipLaunchKernelGGL((decode_attn_kernel<T, OM, 2>), grid, dim3(256), lds, stream, qkv, ldqkv, Hq, Hkv, inv_freq, rope_tab, pos, (T*)kc, (T*)vc, block_table, max_pages, page, scale, (T*)out, ldo, B); } while (0)
+#define DA(T, OM) do { if (one_head) hipLaunchKernelGGL((decode_attn_kernel<T, OM, 1>), grid, dim3(256), lds, stream, qkv, ldqkv, Hq, Hkv, inv_freq, rope_tab, pos, (T*)kc, (T*)vc, block_table, max_pages, page, scale, (T*)out, ldo, B, finished); \
+                       else hipLaunchKernelGGL((decode_attn_kernel<T, OM, 2>), grid, dim3(256), lds, stream, qkv, ldqkv, Hq, Hkv, inv_freq, rope_tab, pos, (T*)kc, (T*)vc, block_table, max_pages, page, scale, (T*)out, ldo, B, finished); } while (0)
     if (dtype == MMX_BF16 && page == 16 && Hq == 7 * Hkv && gqa_shared) {
         const size_t lds2 = (2 * 16 * 64 + 2 * 64) * 2 + (4 * 8 * 16 * 8 + 3 * 32 + 32 * 7 * 64 + (size_t)max_pages) * 4;
         MMX_CHECK_ARG(lds2 <= 160 * 1024);
         if (out_packed) MMX_LDS_OPT_IN((decode_attn_gqa_kernel<true, 7>), lds2);
         else MMX_LDS_OPT_IN((decode_attn_gqa_kernel<false, 7>), lds2);
-#define DG(OPK) hipLaunchKernelGGL((decode_attn_gqa_kernel<OPK, 7>), dim3(Hkv * B), dim3(256), lds2, stream, qkv, ldqkv, Hq, Hkv, inv_freq, rope_tab, pos, (bf16_t*)kc, (bf16_t*)vc, block_table, max_pages, scale, (bf16_t*)out, ldo, B)
+#define DG(OPK) hipLaunchKernelGGL((decode_attn_gqa_kernel<OPK, 7>), dim3(Hkv * B), dim3(256), lds2, stream, qkv, ldqkv, Hq, Hkv, inv_freq, rope_tab, pos, (bf16_t*)kc, (bf16_t*)vc, block_table, max_pages, scale, (bf16_t*)out, ldo, B, finished)
         if (out_packed) DG(true); else DG(false);
     } else if (dtype == MMX_BF16) { if (out_packed) DA(bf16_t, 1); else DA(bf16_t, 0); }
     else if (dtype == MMX_F32) { if (split_h2) DA(float, 3); else if (split_out) DA(float, 2); else if (out_packed) DA(float, 1); else DA(float, 0); }
     else return MMX_EARG;
     MMX_LAUNCH_CHECK();
     return MMX_OK;
+}
+extern "C" int mmx_decode_attn(const float* qkv, int64_t ldqkv, int B, int Hq, int Hkv, int D, const float* inv_freq,
+                               const float* rope_tab, const int32_t* pos, void* kc, void* vc, const int32_t* block_table, int max_pages,
+                               int page, float scale, void* out, int64_t ldo, int dtype, int out_packed, hipStream_t stream) {
+    return mmx_decode_attn_fin(qkv, ldqkv, B, Hq, Hkv, D, inv_freq, rope_tab, pos, nullptr, kc, vc, block_table, max_pages, page, scale,
+                               out, ldo, dtype, out_packed, stream);
 }

@@ -137,6 +137,9 @@ class LlmEngine:
     # (csrc/elementwise.hip prefetch_kernel), so that the next projections read them from the Infinity Cache; 0 = off, else the
     # number of workgroups of the prefetch launch
     prefetch = 0
+    # decode attention returns at once for a slot whose sequence has ended (mmx_decode_attn_fin); False: it recomputes the
+    # slot's last step every step, as before (A/B measurements; the live slots' results are the same bit for bit)
+    skip_finished = True
 
     def __init__(self, sd: Dict[str, torch.Tensor], dtype=BF16, device="cuda", max_batch=1, max_ctx=2048, page=16,
                  heads=14, kv_heads=2, head_dim=64, rope_theta=1e6, eps=1e-6, speech_token_size=6561, use_graphs=True,
@@ -306,6 +309,9 @@ class LlmEngine:
         dt, H, I, c, S = m.ddt, m.H, m.I, self.v2_cfg, self._planes()
         NQ = (m.Hq + 2 * m.Hkv) * m.D
         qkv = S["qkv"][:B]
+        # the attention of an ended slot is skipped: the sampler leaves such a slot's state and input alone and nothing reads its
+        # rows (rows are independent in every projection), until admit / compact_from / _upload_state rewrite the whole column
+        fin = self.state[ST_FIN] if self.skip_finished else None      # (pos is state[ST_POS]: _decode_step)
         ops.decode_prep(x_in, S["xs_a"], S["ssq_a"], B=B, K=H, gamma=m.layers[0]["g1"], h=h, dtype=dt)
         for l, w in enumerate(m.layers):
             self._prefetch(l)
@@ -315,7 +321,7 @@ class LlmEngine:
             # (bf16 build: one plane = the packed A-fragment order the attention kernels already write)
             ops.decode_attn(qkv, m.inv_freq, pos, m.kc[l], m.vc[l], block_table, S["xs_att"], B=B, Hq=m.Hq,
                             Hkv=m.Hkv, page=m.page, dtype=m.dtype, rope_tab=m.rope_tab, per_head=(m.split or B < self.gqa_min_batch),
-                            out_split=("f16" if m.h2 else m.split), out_packed=not m.split)
+                            out_split=("f16" if m.h2 else m.split), out_packed=not m.split, finished=fin)
             ops.skinny2(S["xs_att"], w["wo"], B=B, K=m.Hq * m.D, N=H, dtype=dt, epi=2, out=h, xs_out=S["xs_b"],
                         gamma_next=w["g2"], ssq_out=S["ssq_b"], tiles_per_wg=c["o"][0])
             ops.skinny2(S["xs_b"], w["wgu"], B=B, K=H, N=I, dtype=dt, ssq_in=S["ssq_b"], eps=m.eps, epi=1, xs_out=S["xs_act"],
