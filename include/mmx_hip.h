@@ -464,10 +464,12 @@ int mmx_est_resnet(const MmxEstResnetParams* p, int dtype, int bm, int cfg, hipS
 /* ---------------------------------------------------------------------------------------------
  * DAC-VAE ResidualUnit as one kernel (dac-vae/model.py:107-143; :509-514: LeakyReLU(slope) after every Conv1d):
  *     x_out = x + lrelu(conv1(snake_a2(lrelu(conv7, dilation dil (snake_a0(x))))))      [act_out = snake_alpha_next(x_out)]
- * for the narrow decoder stages, C = 48 / 96 / 192; dtype MMX_BF16 or MMX_X2 (the fp32 build runs the unit as two
+ * for the narrow decoder stages, C = 48 / 96 / 192, and the encoder's first two, C = 64 / 128 (MMX_BF16 and MMX_X2 only: the
+ * encoder has no weight planes, MMX_X2W with C = 64 / 128 is MMX_EARG); dtype MMX_BF16 or MMX_X2 (the fp32 build runs the unit as two
  * mmx_gemm_win launches).  x / x_out: fp32 [B][T][C] residual stream (batch stride x_bs elements; x_out must not alias x:
  * neighbouring tiles read each other's halo rows); act_out (optional): the next layer's input activation, bf16 (MMX_BF16) or
- * fp32 (MMX_X2), same strides.  w7 / w1: mmx_pack_skinny packs of the weight matrices [C][7 * CP] (tap-major, each tap's
+ * fp32 (MMX_X2), same strides.  x_out may be NULL when act_out is given (the last unit of an encoder block, whose residual
+ * stream nobody reads): nothing is written for it and act_out keeps the bits it has with x_out; both NULL is MMX_EARG.  w7 / w1: mmx_pack_skinny packs of the weight matrices [C][7 * CP] (tap-major, each tap's
  * C input channels zero-padded to CP = 32 * ceil(C / 32)) and [C][CP].  lens (optional, int32 [B]): rows >= lens[b] of batch
  * member b are conv padding - read as zero, written as zero (utterances of different lengths decoded in one batch).
  * bm: rows per workgroup, 0 = the library's default for (C, dtype); a height the build has no instantiation for is MMX_EARG

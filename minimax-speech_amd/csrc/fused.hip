@@ -1043,15 +1043,21 @@ __global__ __launch_bounds__(64 * NW) void est_resnet_kernel(MmxEstResnetParams 
 // 4 waves as WR row groups x WC column groups of 48 columns (3 n-fragments) each: C = 192 -> 1 x 4 (every weight
 // fragment streamed once per workgroup), 96 -> 2 x 2, 48 -> 4 x 1.  CP = channels padded to a multiple of 32 (48 -> 64,
 // zero columns in both tiles, zero weight columns).
+// The encoder's first two stages (C = 64 / 128, mmx/dac.py DacEncoderEngine(fuse_ru=True)) take the same wave grids with
+// NF = C / (16 * WC) = 4 n-fragments per wave: 64 -> 4 x 1, 128 -> 2 x 2, 64 columns per wave and 16 per lane in the
+// epilogues (NF = 2 is the other grid each of them allows, 2 x 2 / 1 x 4 of 32 columns; no form uses it).
 // LDS row pitch of a [rows][cp] bf16 tile: the smallest odd multiple of 32 bytes that holds a row (conflict-free
 // ds_read_b128 fragment reads, like the 96 / 160-byte pitches of csrc/gemm.hip)
 __host__ __device__ constexpr int dac_pitch(int cp) { return (((cp * 2 + 31) / 32) | 1) * 32; }
-constexpr int DAC_PATCH_FLOATS = 16 * 52;              // per wave: 48 columns + 4
+// per wave: 16 rows of the widest slice of the channel count's forms + 4 (48 columns for C = 48 / 96 / 192, 64 for C = 64 / 128)
+__host__ __device__ constexpr int dac_patch_floats(int C) { return 16 * ((C % 48 == 0 ? 48 : 64) + 4); }
 
-template <int C, int BM, int WR, int WC, int NS, int PF, bool WP = false>
+template <int C, int BM, int WR, int WC, int NS, int PF, bool WP = false, int NF = C / (16 * WC)>
 __global__ __launch_bounds__(256) void dac_ru_kernel(MmxDacRuParams p) {
     typedef bf16_t T;
-    constexpr int E = 8, KB = 32, NF = 3, CP = (C + 31) / 32 * 32, PA = dac_pitch(CP);
+    constexpr int E = 8, KB = 32, CP = (C + 31) / 32 * 32, PA = dac_pitch(CP);
+    constexpr int NC = 4 * NF, WCOLS = 16 * NF, DAC_PATCH_FLOATS = dac_patch_floats(C);   // columns per lane (epilogues) / per wave
+    static_assert(NF >= 2 && NF <= 4 && 16 * (WCOLS + 4) <= DAC_PATCH_FLOATS, "n-fragments per wave / patch");
     constexpr int BMW = BM / WR, MF = BMW / 16;
     constexpr int NK7 = 7 * CP / KB, NK1 = CP / KB;
     constexpr bool PRECISE = NS > 1;
@@ -1142,54 +1148,50 @@ __global__ __launch_bounds__(256) void dac_ru_kernel(MmxDacRuParams p) {
         }
     }
     __syncthreads();
-    // ---- conv k7, dilation d: rows wr*BMW .., columns wc*48 ..
+    // ---- conv k7, dilation d: rows wr*BMW .., columns wc*WCOLS ..
     {
         float4_t acc[MF][NF];
         zero_acc(acc);
         stage_run_w<T, MF, NF, PF, NS, NF, WP>(ring, ain + (wr * BMW + l16) * PA + g * 16, PA, CP / KB, w7_w, ns7, NK7, (long)C * 7 * CP, w1_w, ns1, NK1, NF, acc, PLA, d * PA);
-        // + bias -> LeakyReLU -> Snake(a2) -> mid (row layout through the wave's patch: 12 consecutive columns per lane)
-        const int col = wc * 48 + (lane & 3) * 12;
-        float b7[12], a2[12], i2[12];
-        loadn<12>(prm + 2 * CP + col, b7);
-        loadn<12>(prm + 1 * CP + col, a2);
-        loadn<12>(prm + 6 * CP + col, i2);
+        // + bias -> LeakyReLU -> Snake(a2) -> mid (row layout through the wave's patch: NC = 4 NF consecutive columns per lane)
+        const int col = wc * WCOLS + (lane & 3) * NC;
+        float b7[NC], a2[NC], i2[NC];
+        loadn<NC>(prm + 2 * CP + col, b7);
+        loadn<NC>(prm + 1 * CP + col, a2);
+        loadn<NC>(prm + 6 * CP + col, i2);
 #pragma unroll
         for (int i = 0; i < MF; ++i) {
-            float v[12];
+            float v[NC];
             to_rows<NF>(acc[i], patch, lane, v);
 #pragma unroll
-            for (int c = 0; c < 12; ++c) {
+            for (int c = 0; c < NC; ++c) {
                 float y = v[c] + b7[c];
                 y = y > 0.f ? y : y * p.slope;
                 v[c] = snk(y, a2[c], i2[c]);
             }
             char* dst = mid + (wr * BMW + i * 16 + rl) * PA + col * 2;
-            uint2 h0, h1, h2;
-            h0.x = pack_bf16x2(v[0], v[1]); h0.y = pack_bf16x2(v[2], v[3]);
-            h1.x = pack_bf16x2(v[4], v[5]); h1.y = pack_bf16x2(v[6], v[7]);
-            h2.x = pack_bf16x2(v[8], v[9]); h2.y = pack_bf16x2(v[10], v[11]);
-            *reinterpret_cast<uint2*>(dst) = h0;
-            *reinterpret_cast<uint2*>(dst + 8) = h1;
-            *reinterpret_cast<uint2*>(dst + 16) = h2;
-            if constexpr (NS > 1) {
-                const unsigned w[6] = {h0.x, h0.y, h1.x, h1.y, h2.x, h2.y};
-                unsigned l[6];
+            unsigned w[NC / 2];
 #pragma unroll
-                for (int e = 0; e < 6; ++e)
+            for (int e = 0; e < NC / 2; ++e) w[e] = pack_bf16x2(v[2 * e], v[2 * e + 1]);
+#pragma unroll
+            for (int e = 0; e < NC / 4; ++e) *reinterpret_cast<uint2*>(dst + 8 * e) = make_uint2(w[2 * e], w[2 * e + 1]);
+            if constexpr (NS > 1) {
+                unsigned l[NC / 2];
+#pragma unroll
+                for (int e = 0; e < NC / 2; ++e)
                     l[e] = pack_bf16x2(v[2 * e] - __uint_as_float(w[e] << 16), v[2 * e + 1] - __uint_as_float(w[e] & 0xffff0000u));
-                *reinterpret_cast<uint2*>(dst + PLM) = make_uint2(l[0], l[1]);
-                *reinterpret_cast<uint2*>(dst + PLM + 8) = make_uint2(l[2], l[3]);
-                *reinterpret_cast<uint2*>(dst + PLM + 16) = make_uint2(l[4], l[5]);
+#pragma unroll
+                for (int e = 0; e < NC / 4; ++e) *reinterpret_cast<uint2*>(dst + PLM + 8 * e) = make_uint2(l[2 * e], l[2 * e + 1]);
             }
         }
     }
     // residual rows of the closing epilogue (issued before the 1x1 stage: see est_tail_kernel on vmcnt order)
-    const int col = wc * 48 + (lane & 3) * 12;
-    float xr[MF][12];
+    const int col = wc * WCOLS + (lane & 3) * NC;
+    float xr[MF][NC];
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
         const int t = t0 + wr * BMW + i * 16 + rl;
-        loadn<12>(xb + (long)(t < lc ? t : lc - 1) * C + col, xr[i]);
+        loadn<NC>(xb + (long)(t < lc ? t : lc - 1) * C + col, xr[i]);
     }
     __syncthreads();
     // ---- conv k1 + bias -> LeakyReLU -> + x -> x_out [-> Snake(alpha_next) -> act_out]
@@ -1197,39 +1199,35 @@ __global__ __launch_bounds__(256) void dac_ru_kernel(MmxDacRuParams p) {
         float4_t acc[MF][NF];
         zero_acc(acc);
         stage_run_w<T, MF, NF, PF, NS, NF, WP>(ring, mid + (wr * BMW + l16) * PA + g * 16, PA, NK1, w1_w, ns1, NK1, (long)C * CP, (const T*)nullptr, 0, 0, NF, acc, PLM);
-        float b1[12], an[12], in[12];
-        loadn<12>(prm + 3 * CP + col, b1);
-        loadn<12>(prm + 4 * CP + col, an);
-        loadn<12>(prm + 7 * CP + col, in);
-        float* xo = p.x_out + (long)b * p.x_bs;
+        float b1[NC], an[NC], in[NC];
+        loadn<NC>(prm + 3 * CP + col, b1);
+        loadn<NC>(prm + 4 * CP + col, an);
+        loadn<NC>(prm + 7 * CP + col, in);
+        float* xo = p.x_out ? p.x_out + (long)b * p.x_bs : nullptr;   // NULL: the caller wants act_out only
 #pragma unroll
         for (int i = 0; i < MF; ++i) {
-            float v[12];
+            float v[NC];
             to_rows<NF>(acc[i], patch, lane, v);
             const int t = t0 + wr * BMW + i * 16 + rl;
             const bool live = t < len;
 #pragma unroll
-            for (int c = 0; c < 12; ++c) {
+            for (int c = 0; c < NC; ++c) {
                 float y = v[c] + b1[c];
                 y = y > 0.f ? y : y * p.slope;
                 v[c] = live ? y + xr[i][c] : 0.f;
             }
             if (t < p.T) {
-                storen<12>(xo + (long)t * C + col, v);
+                if (xo) storen<NC>(xo + (long)t * C + col, v);
                 if (p.act_out) {
 #pragma unroll
-                    for (int c = 0; c < 12; ++c) v[c] = snk(v[c], an[c], in[c]);
+                    for (int c = 0; c < NC; ++c) v[c] = snk(v[c], an[c], in[c]);
                     TA* ao = reinterpret_cast<TA*>(p.act_out) + (long)b * p.x_bs + (long)t * C + col;
                     if constexpr (NS == 1) {
-                        uint2 h0, h1, h2;
-                        h0.x = pack_bf16x2(v[0], v[1]); h0.y = pack_bf16x2(v[2], v[3]);
-                        h1.x = pack_bf16x2(v[4], v[5]); h1.y = pack_bf16x2(v[6], v[7]);
-                        h2.x = pack_bf16x2(v[8], v[9]); h2.y = pack_bf16x2(v[10], v[11]);
-                        *reinterpret_cast<uint2*>(ao) = h0;
-                        *reinterpret_cast<uint2*>(ao + 4) = h1;
-                        *reinterpret_cast<uint2*>(ao + 8) = h2;
+#pragma unroll
+                        for (int e = 0; e < NC / 4; ++e)
+                            *reinterpret_cast<uint2*>(ao + 4 * e) = make_uint2(pack_bf16x2(v[4 * e], v[4 * e + 1]), pack_bf16x2(v[4 * e + 2], v[4 * e + 3]));
                     } else {
-                        storen<12>(reinterpret_cast<float*>(ao), v);
+                        storen<NC>(reinterpret_cast<float*>(ao), v);
                     }
                 }
             }
@@ -1245,7 +1243,7 @@ __global__ __launch_bounds__(256) void dac_ru_kernel(MmxDacRuParams p) {
 constexpr size_t LDS_MAX = 160 * 1024;
 constexpr size_t dac_ru_lds(int C, int bm, int ns, int dil) {
     const int CP = (C + 31) / 32 * 32, PA = dac_pitch(CP);
-    return (size_t)ns * ((size_t)(bm + 6 * dil) * PA + (size_t)bm * PA) + 4 * DAC_PATCH_FLOATS * 4 + 8 * CP * 4;
+    return (size_t)ns * ((size_t)(bm + 6 * dil) * PA + (size_t)bm * PA) + 4 * dac_patch_floats(C) * 4 + 8 * CP * 4;
 }
 constexpr size_t tail_lds(int esz, int bm, int nw, int ns) {
     if (ns == 2 && bm == 64 && esz == 2)               // the split build's 64-row tile (HK in est_tail_tile)
@@ -1441,13 +1439,25 @@ constexpr DacRuForm DAC_RU_FORMS[] = {
     dac_ru_form<192, 32, 1, 4, 2, 2>(), dac_ru_form<192, 16, 1, 4, 2, 2>(),
     dac_ru_form<48, 64, 4, 1, 2, 2, true>(), dac_ru_form<96, 128, 2, 2, 2, 3, true>(), dac_ru_form<96, 64, 2, 2, 2, 3, true>(),   // weight planes
     dac_ru_form<192, 32, 1, 4, 2, 2, true>(),
+    // the encoder's 64- and 128-channel stages (no weight planes: the encoder has none), 64 columns per wave.  C = 128: a
+    // 256-row tile would be 8 m-fragments x 4 n-fragments of accumulators per wave, and the split build's 128-row tile
+    // does not fit at dilation 9 (178 KB by dac_ru_lds; 64 rows: 123 KB)
+    dac_ru_form<64, 256, 4, 1, 1, 2>(), dac_ru_form<64, 128, 4, 1, 1, 2>(), dac_ru_form<64, 64, 4, 1, 1, 2>(),          // bf16 build
+    dac_ru_form<128, 128, 2, 2, 1, 2>(), dac_ru_form<128, 64, 2, 2, 1, 2>(),
+    dac_ru_form<64, 128, 4, 1, 2, 2>(), dac_ru_form<64, 64, 4, 1, 2, 2>(),                                              // split build
+    dac_ru_form<128, 64, 2, 2, 2, 2>(), dac_ru_form<128, 32, 2, 2, 2, 2>(),
 };
+// every form fits the CU's LDS at the widest dilation the entry point accepts
+static_assert(dac_ru_lds(64, 256, 1, 9) <= LDS_MAX && dac_ru_lds(128, 128, 1, 9) <= LDS_MAX && dac_ru_lds(64, 128, 2, 9) <= LDS_MAX);
+static_assert(dac_ru_lds(128, 64, 2, 9) <= LDS_MAX && dac_ru_lds(128, 128, 2, 9) > LDS_MAX);
 // dtype: MMX_X2 for MMX_X2W, which sets wp (w7 / w1 are [hi pack | lo pack])
 constexpr const DacRuForm* dac_ru_select(int dtype, bool wp, int bm, int C, int dil) {
     // tile heights: default = the measured best of tools/dac_lab.py for (C, dtype); smaller tiles let two workgroups share a
     // CU (LDS, 256 registers), which overlaps one's load / epilogue phases with the other's MFMA stages
-    const int dflt = dtype == MMX_BF16 ? (C == 48 ? 128 : C == 96 ? 256 : dil > 3 ? 32 : 64)
-                   : dtype == MMX_X2   ? (C == 48 ? 64 : C == 96 ? (dil > 3 ? 128 : 64) : 32) : 0;
+    // C = 64 / 128 (encoder): not measured per tile; by the byte arithmetic they take the tile of the nearest measured width whose
+    // form exists - 64 that of 48 (the same CP = 64 tiles and weight packs), 128 the largest that fits every dilation
+    const int dflt = dtype == MMX_BF16 ? (C == 48 || C == 64 || C == 128 ? 128 : C == 96 ? 256 : dil > 3 ? 32 : 64)
+                   : dtype == MMX_X2   ? (C == 48 || C == 64 || C == 128 ? 64 : C == 96 ? (dil > 3 ? 128 : 64) : 32) : 0;
     if (wp && bm != 0 && bm != dflt) return nullptr;   // weight planes: the split build's default tile per stage, and no other
     return find_form(DAC_RU_FORMS, dtype, wp, bm ? bm : dflt, 0, 0, 0, C);
 }
@@ -1458,6 +1468,10 @@ static_assert(dac_ru_select(MMX_X2, false, 0, 48, 9)->launch == launch_dac_ru<48
 static_assert(dac_ru_select(MMX_X2, false, 0, 96, 3)->launch == launch_dac_ru<96, 64, 2, 2, 2, 3, false> && dac_ru_select(MMX_X2, false, 0, 96, 9)->launch == launch_dac_ru<96, 128, 2, 2, 2, 3, false>);
 static_assert(dac_ru_select(MMX_X2, true, 0, 48, 9)->launch == launch_dac_ru<48, 64, 4, 1, 2, 2, true> && dac_ru_select(MMX_X2, true, 0, 192, 9)->launch == launch_dac_ru<192, 32, 1, 4, 2, 2, true>);
 static_assert(dac_ru_select(MMX_X2, true, 0, 96, 3)->launch == launch_dac_ru<96, 64, 2, 2, 2, 3, true> && dac_ru_select(MMX_X2, true, 0, 96, 9)->launch == launch_dac_ru<96, 128, 2, 2, 2, 3, true>);
+// the encoder's stages (DacEncoderEngine(fuse_ru=True)): one tile per (dtype, C) whatever the dilation
+static_assert(dac_ru_select(MMX_BF16, false, 0, 64, 1)->launch == launch_dac_ru<64, 128, 4, 1, 1, 2, false> && dac_ru_select(MMX_BF16, false, 0, 128, 9)->launch == launch_dac_ru<128, 128, 2, 2, 1, 2, false>);
+static_assert(dac_ru_select(MMX_X2, false, 0, 64, 9)->launch == launch_dac_ru<64, 64, 4, 1, 2, 2, false> && dac_ru_select(MMX_X2, false, 0, 128, 9)->launch == launch_dac_ru<128, 64, 2, 2, 2, 2, false>);
+static_assert(dac_ru_select(MMX_X2, true, 0, 64, 1) == nullptr && dac_ru_select(MMX_X2, true, 0, 128, 1) == nullptr);
 
 }  // namespace
 
@@ -1505,8 +1519,9 @@ extern "C" int mmx_est_resnet(const MmxEstResnetParams* pp, int dtype, int bm, i
 extern "C" int mmx_dac_ru(const MmxDacRuParams* pp, int dtype, int bm, hipStream_t stream) {
     MMX_CHECK_ARG(pp != nullptr);
     const MmxDacRuParams& p = *pp;
-    MMX_CHECK_ARG(p.x && p.x_out && p.x != p.x_out && p.w7 && p.w1 && p.b7 && p.b1 && p.a0 && p.a2 && p.B > 0 && p.T > 0);
-    MMX_CHECK_ARG(p.dil >= 1 && p.dil <= 9 && (p.C == 48 || p.C == 96 || p.C == 192) && p.x_bs % 4 == 0 && p.x_bs >= (int64_t)p.T * p.C);
+    // x_out may be NULL when act_out is given: the last unit of an encoder block, whose residual stream nobody reads
+    MMX_CHECK_ARG(p.x && (p.x_out || p.act_out) && p.x != p.x_out && p.w7 && p.w1 && p.b7 && p.b1 && p.a0 && p.a2 && p.B > 0 && p.T > 0);
+    MMX_CHECK_ARG(p.dil >= 1 && p.dil <= 9 && (p.C == 48 || p.C == 64 || p.C == 96 || p.C == 128 || p.C == 192) && p.x_bs % 4 == 0 && p.x_bs >= (int64_t)p.T * p.C);
     MMX_CHECK_ARG(((uintptr_t)p.x % 16) == 0 && ((uintptr_t)p.x_out % 16) == 0 && ((uintptr_t)p.act_out % 16) == 0 && ((uintptr_t)p.a0 % 16) == 0);
     MMX_CHECK_ARG(!p.act_out || p.alpha_next);
     const bool wplanes = dtype == MMX_X2W;             // w7 / w1 are [hi pack | lo pack]

@@ -43,6 +43,44 @@ def latent_record(model, audio, sample_rate: int, original_path: str = "") -> Di
     }
 
 
+@torch.inference_mode()
+def latent_records(model, audios, sample_rate: int, original_paths: List[str] = None) -> List[Dict]:
+    """latent_record for a list of mono waveforms of any lengths in ONE encode (model.encode_batch: a zero-padded batch whose
+    members keep the values of their own unpadded encode): the dict of latent_record per clip, same clamp, same fields."""
+    if sample_rate != model.sample_rate:
+        raise ValueError(f"audio must be resampled to {model.sample_rate} Hz first (got {sample_rate})")
+    if original_paths is not None and len(original_paths) != len(audios):
+        raise ValueError(f"{len(original_paths)} paths for {len(audios)} clips")
+    dev = next(model.parameters()).device
+    clips = [torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).float().reshape(-1) for a in audios]
+    outs = model.encode_batch([torch.clamp(c.to(dev), -1.0, 1.0) for c in clips])
+    recs = []
+    for i, (c, (z, mu, logs)) in enumerate(zip(clips, outs)):
+        z, mu, logs = z.cpu(), mu.cpu(), logs.cpu()
+        n = c.numel()
+        recs.append({
+            "z": z, "mu": mu, "logs": logs,
+            "sample_rate": sample_rate,
+            "compression_ratio": n // z.shape[-1],
+            "original_duration": n / sample_rate,
+            "original_samples": n,
+            "latent_shape": list(z.shape),
+            "original_path": original_paths[i] if original_paths is not None else "",
+        })
+    return recs
+
+
+def save_latents(model, audios, sample_rate: int, audio_paths: List[str]) -> List[str]:
+    """latent_records, each written as `<audio stem>_latent2x.pt` next to its audio file; returns the paths written."""
+    outs = []
+    for rec, path in zip(latent_records(model, audios, sample_rate, audio_paths), audio_paths):
+        out = latent_path(path)
+        os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+        torch.save(rec, out)
+        outs.append(out)
+    return outs
+
+
 def save_latent(model, audio, sample_rate: int, audio_path: str) -> str:
     """Encodes and writes `<audio stem>_latent2x.pt` next to the audio file; returns the path written."""
     rec = latent_record(model, audio, sample_rate, audio_path)

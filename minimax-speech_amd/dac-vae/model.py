@@ -98,11 +98,25 @@ class DACVAE(EngineHost):
     def encode(self, audio_data: torch.Tensor, training: bool = True, noise: torch.Tensor = None):
         """audio [B, 1, T] (T a hop multiple, see preprocess) -> (z, m, logs), each [B, latent_dim, T/hop]
         (model.py:469-483).  `noise` optionally supplies the randn_like(m) draw (parity tests)."""
+        return self._encoder().encode(audio_data.float(), noise=noise, generator=self.noise_generator)
+
+    def _encoder(self):
         from mmx.dac import DacEncoderEngine
-        dev = self._device()
         if self._enc_engine is None:
-            self._enc_engine = DacEncoderEngine(self.state_dict(), self.encoder_rates, dtype=self.compute_dtype, device=dev)
-        return self._enc_engine.encode(audio_data.float(), noise=noise, generator=self.noise_generator)
+            self._enc_engine = DacEncoderEngine(self.state_dict(), self.encoder_rates, dtype=self.compute_dtype, device=self._device(),
+                                                fuse_ru=getattr(self, "encoder_fused", False))
+        return self._enc_engine
+
+    @torch.inference_mode()
+    def encode_batch(self, audios, noises=None):
+        """Clips of different lengths, a list of [1, 1, T_b] or [T_b] on the device, in ONE zero-padded batch
+        (DacEncoderEngine.encode_ragged) -> a list of (z, m, logs): member b's are those of encode(audios[b]) bit for bit,
+        [1, latent_dim, T'_b] for a [1, 1, T_b] clip and [latent_dim, T'_b] for a [T_b] one.  Unpadded clips floor their length
+        at every strided conv, as encode does.  noises[b] [latent_dim, T'_b] (or with a leading 1) supplies member b's draw."""
+        if noises is not None:
+            noises = [n.reshape(n.shape[-2], n.shape[-1]) for n in noises]
+        outs = self._encoder().encode_ragged([a.float().reshape(-1) for a in audios], noises=noises, generator=self.noise_generator)
+        return [tuple(t[None] if a.dim() == 3 else t for t in o) for a, o in zip(audios, outs)]
 
     @torch.inference_mode()
     def forward(self, audio_data: torch.Tensor, sample_rate: int = 24000):

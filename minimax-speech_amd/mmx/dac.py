@@ -178,10 +178,19 @@ class DacEncoderEngine:
 
     Same mapping as the decoder: one windowed-GEMM launch per Conv1d, the strided down-sampling convs
     (EncoderBlock, :182-188: k=2s, stride s, pad ceil(s/2)) through MmxGemmParams.row_stride; the d_in=1 head is its
-    own kernel (K=7 is no GEMM).  31 GEMM launches + head + VAE-sampling kernel + 3 layout copies."""
+    own kernel (K=7 is no GEMM).  31 GEMM launches + head + VAE-sampling kernel + 3 layout copies.
 
-    def __init__(self, sd: Dict[str, torch.Tensor], rates: List[int], dtype=BF16, device="cuda"):
+    fuse_ru=True (bf16 and split builds; the fp32 build ignores it, as the decoder does): the ResidualUnits of the 64- and
+    128-channel stages - the widest tensors of the model, 24 kHz x 64 and 12 kHz x 128 - run as ONE kernel each (mmx_dac_ru)
+    instead of two GEMM launches: 12 GEMM launches become 6.  Off by default: the fused units round the same operands but
+    take the bf16 build's sines with the fast intrinsic, so their outputs are not today's bits.
+
+    encode_ragged takes clips of different lengths as one zero-padded batch; every member gets the bits of its own encode."""
+    FUSED_RU_C = (64, 128)        # channel counts mmx_dac_ru has encoder forms for
+
+    def __init__(self, sd: Dict[str, torch.Tensor], rates: List[int], dtype=BF16, device="cuda", fuse_ru=False):
         self.dtype, self.tdt, self.dev = dtype, TORCH_DT[dtype], torch.device(device)
+        self.fuse_ru = bool(fuse_ru) and dtype in (BF16, X2)
         self.rates = list(rates)
         self.hop = int(math.prod(rates))
         f = lambda k: sd[k].detach().to(self.dev, torch.float32)
@@ -200,11 +209,16 @@ class DacEncoderEngine:
             q = f"{p}.{1 + i}.block"
             blk = dict(stride=s, c=c, rus=[], alpha_out=alpha(q + ".3.alpha"), wd=ops.pack_conv1d(wn(q + ".4.0"), dtype),
                        bd=bias(q + ".4.0"))
+            blk["fused"] = self.fuse_ru and c in self.FUSED_RU_C
             for j, d in enumerate((1, 3, 9)):
                 r = f"{q}.{j}.block"
-                blk["rus"].append(dict(dil=d, a0=alpha(r + ".0.alpha"), w7=ops.pack_conv1d(wn(r + ".1.0"), dtype),
-                                       b7=bias(r + ".1.0"), a2=alpha(r + ".2.alpha"),
-                                       w1=ops.pack_conv1d(wn(r + ".3.0"), dtype), b1=bias(r + ".3.0")))
+                w7, w1 = wn(r + ".1.0"), wn(r + ".3.0")
+                ru = dict(dil=d, a0=alpha(r + ".0.alpha"), b7=bias(r + ".1.0"), a2=alpha(r + ".2.alpha"), b1=bias(r + ".3.0"))
+                if blk["fused"]:
+                    ru["w7_p"], ru["w1_p"] = ops.pack_dac_ru(w7, w1, dtype)
+                else:
+                    ru["w7"], ru["w1"] = ops.pack_conv1d(w7, dtype), ops.pack_conv1d(w1, dtype)
+                blk["rus"].append(ru)
             self.blocks.append(blk)
             c *= 2
         n = len(rates)
@@ -229,44 +243,69 @@ class DacEncoderEngine:
                 return 0
         return T
 
-    @torch.no_grad()
-    def encode(self, audio: torch.Tensor, noise: torch.Tensor = None, generator: torch.Generator = None):
-        """audio [B, 1, T] fp32 cuda -> (z, mu, logs), each [B, D, T'] fp32; T' = T/hop for a hop multiple
-        (DACVAE.preprocess), else each stride-s conv floors as torch's Conv1d does (extract_dac_latents.py:20-36
-        encodes unpadded audio).  `noise` [B, D, T'] stands for the reference's torch.randn_like(m); drawn on the
-        device when absent."""
-        assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 3 and audio.shape[1] == 1
-        B, _, T = audio.shape
-        if self.frames(T) < 1:
-            raise ValueError(f"audio of {T} samples is shorter than one latent frame")
+
+    def stage_lens(self, n: int) -> List[int]:
+        """Rows a clip of n samples has after the head and after each stride-s conv: [n, _down(n, s0), ...] (floors as torch's
+        Conv1d takes them; the last entry is frames(n) where that is at least 1)."""
+        out = [int(n)]
+        for s in self.rates:
+            out.append(self._down(out[-1], s))
+        return out
+
+    def _run(self, audio, B, T, noise_t, generator, lens=None):
+        """audio [B, 1, T] contiguous -> time-major (z, mu, logs) [B, T', D].  lens (ints, optional): a ZERO-PADDED batch whose
+        member b has lens[b] <= T samples.  Every layer then leaves the rows beyond a member's length as the zero padding an
+        encode of that member alone would see: a row-mask launch on the head's outputs, the row mask of the OUTPUT length in
+        the epilogue of every unit conv and strided conv, the lengths themselves in the fused units."""
         dt, tdt, dev = self.dtype, self.tdt, self.dev
         new = lambda t, c, d=None: torch.empty(B, t, c, dtype=(d or tdt), device=dev)
-        audio = audio.contiguous()
+        if lens is not None:
+            chain = [self.stage_lens(n) for n in lens]           # [member][stage]
+            lens_at = lambda st: torch.tensor([c[st] for c in chain], dtype=torch.int32, device=dev)
+            mask_of = lambda ln, t: (torch.arange(t, device=dev)[None, :] < ln[:, None]).float().contiguous()
+        ln = lens_at(0) if lens is not None else None
+        rm = mask_of(ln, T) if lens is not None else None
         x = new(T, self.C0, torch.float32)
-        a = new(T, self.C0)
+        a = None if self.blocks[0]["fused"] else new(T, self.C0)     # a fused unit takes Snake(x) itself
         ops.conv_cin1(audio, self.w0, self.b0, T=T, C_=self.C0, k=self.k0, batch=B, dtype=dt,
-                      alpha=self.blocks[0]["rus"][0]["a0"], out_f32=x, out_act=a)
+                      alpha=(None if a is None else self.blocks[0]["rus"][0]["a0"]), out_f32=x, out_act=a)
+        if rm is not None:                                       # the head's rows beyond a member's end hold bias + taps
+            ops.mask_rows(x, rm, rows=B * T, C_=self.C0, dtype=F32)
+            if a is not None:
+                ops.mask_rows(a, rm, rows=B * T, C_=self.C0, dtype=dt)
         for bi, blk in enumerate(self.blocks):
             s, c = blk["stride"], blk["c"]
             for j, ru in enumerate(blk["rus"]):
                 d = ru["dil"]
-                hmid = new(T, c)
-                ops.conv1d(a, ru["w7"], T=T, Cin=c, k=7, dil=d, pad_left=3 * d, dtype=dt, batch=B, bias=ru["b7"],
-                           act="lrelu", alpha=ru["a2"], out_act=hmid)
                 last = j == 2
                 nxt = blk["alpha_out"] if last else blk["rus"][j + 1]["a0"]
+                if blk["fused"]:
+                    # one kernel per unit: the fp32 residual stream is all that passes between them, and the last unit writes
+                    # only the strided conv's input activation
+                    x2 = None if last else new(T, c, torch.float32)
+                    a = new(T, c) if last else None
+                    ops.dac_ru(x, x2, ru, B=B, T=T, C_=c, dil=d, dtype=dt, act_out=a, alpha_next=(nxt if last else None), lens=ln)
+                    x = x2
+                    continue
+                hmid = new(T, c)
+                ops.conv1d(a, ru["w7"], T=T, Cin=c, k=7, dil=d, pad_left=3 * d, dtype=dt, batch=B, bias=ru["b7"],
+                           act="lrelu", alpha=ru["a2"], rowmask=rm, out_act=hmid)
                 x2 = None if last else new(T, c, torch.float32)
                 a3 = new(T, c)
                 ops.conv1d(hmid, ru["w1"], T=T, Cin=c, k=1, dtype=dt, batch=B, bias=ru["b1"], act="lrelu",
-                           residual=x, alpha=nxt, out_f32=x2, out_act=a3)
+                           residual=x, alpha=nxt, rowmask=rm, out_f32=x2, out_act=a3)
                 x, a = x2, a3
             T2 = self._down(T, s)
-            nxt = self.blocks[bi + 1]["rus"][0]["a0"] if bi + 1 < len(self.blocks) else self.alpha_final
+            if lens is not None:
+                ln = lens_at(bi + 1)
+                rm = mask_of(ln, T2)
             last_blk = bi + 1 == len(self.blocks)
+            nxt = self.alpha_final if last_blk else self.blocks[bi + 1]["rus"][0]["a0"]
+            nxt_fused = not last_blk and self.blocks[bi + 1]["fused"]
             x = None if last_blk else new(T2, 2 * c, torch.float32)
-            a2 = new(T2, 2 * c)
+            a2 = None if nxt_fused else new(T2, 2 * c)
             ops.conv1d(a, blk["wd"], T=T, Cin=c, k=2 * s, pad_left=math.ceil(s / 2), stride=s, T_out=T2, dtype=dt,
-                       batch=B, bias=blk["bd"], act="lrelu", alpha=nxt, out_f32=x, out_act=a2)
+                       batch=B, bias=blk["bd"], act="lrelu", alpha=(None if nxt_fused else nxt), rowmask=rm, out_f32=x, out_act=a2)
             T, a = T2, a2
         # conv k3 + LeakyReLU(0.1), then F.leaky_relu(0.01) (model.py:475): one LeakyReLU of slope 0.1*0.01
         h = new(T, self.D)
@@ -275,18 +314,75 @@ class DacEncoderEngine:
         ml = new(T, 2 * self.D, torch.float32)
         ops.conv1d(h, self.w_post, T=T, Cin=self.D, k=1, dtype=dt, batch=B, bias=self.b_post, act="lrelu", out_f32=ml)
         D = self.D
-        if noise is None:
+        if noise_t is None:
             noise_t = torch.randn(B, T, D, dtype=torch.float32, device=dev, generator=generator)
-        else:
-            assert noise.shape == (B, D, T)
-            noise_t = torch.empty(B, T, D, dtype=torch.float32, device=dev)
-            noise = noise.to(dev, torch.float32).contiguous()
-            ops.copy2d(noise, F32, D * T, 1, T, noise_t, F32, T * D, D, 1, rows=T, cols=D, batch=B)
         zt, mt, lt = (torch.empty(B, T, D, dtype=torch.float32, device=dev) for _ in range(3))
         ops.vae_sample(ml, noise_t, zt, mt, lt, rows=B * T, D=D)
+        return zt, mt, lt
+
+    @torch.no_grad()
+    def encode(self, audio: torch.Tensor, noise: torch.Tensor = None, generator: torch.Generator = None):
+        """audio [B, 1, T] fp32 cuda -> (z, mu, logs), each [B, D, T'] fp32; T' = T/hop for a hop multiple
+        (DACVAE.preprocess), else each stride-s conv floors as torch's Conv1d does (extract_dac_latents.py:20-36
+        encodes unpadded audio).  `noise` [B, D, T'] stands for the reference's torch.randn_like(m); drawn on the
+        device when absent."""
+        assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 3 and audio.shape[1] == 1
+        B, _, T = audio.shape
+        Tf = self.frames(T)
+        if Tf < 1:
+            raise ValueError(f"audio of {T} samples is shorter than one latent frame")
+        D, dev = self.D, self.dev
+        noise_t = None
+        if noise is not None:
+            assert noise.shape == (B, D, Tf)
+            noise_t = torch.empty(B, Tf, D, dtype=torch.float32, device=dev)
+            noise = noise.to(dev, torch.float32).contiguous()
+            ops.copy2d(noise, F32, D * Tf, 1, Tf, noise_t, F32, Tf * D, D, 1, rows=Tf, cols=D, batch=B)
         outs = []
-        for src in (zt, mt, lt):                               # -> the reference's channels-first [B, D, T]
-            o = torch.empty(B, D, T, dtype=torch.float32, device=dev)
-            ops.copy2d(src, F32, T * D, D, 1, o, F32, D * T, 1, T, rows=T, cols=D, batch=B)
+        for src in self._run(audio.contiguous(), B, T, noise_t, generator):   # -> the reference's channels-first [B, D, T]
+            o = torch.empty(B, D, Tf, dtype=torch.float32, device=dev)
+            ops.copy2d(src, F32, Tf * D, D, 1, o, F32, D * Tf, 1, Tf, rows=Tf, cols=D, batch=B)
             outs.append(o)
         return tuple(outs)
+
+    def check_ragged_args(self, waves, noises=None):
+        """The argument guards of encode_ragged (no kernel runs): -> the member lengths in samples."""
+        if not isinstance(waves, (list, tuple)) or len(waves) == 0:
+            raise ValueError("encode_ragged takes a non-empty list of clips")
+        if noises is not None and len(noises) != len(waves):
+            raise ValueError(f"{len(noises)} noise tensors for {len(waves)} clips")
+        lens = []
+        for b, w in enumerate(waves):
+            if not torch.is_tensor(w) or not (w.dim() == 1 or (w.dim() == 2 and w.shape[0] == 1)):
+                raise ValueError(f"clip {b}: a mono tensor [n] or [1, n] is expected")
+            n = int(w.shape[-1])
+            if self.frames(n) < 1:
+                raise ValueError(f"audio of {n} samples is shorter than one latent frame (clip {b})")
+            if noises is not None and tuple(noises[b].shape) != (self.D, self.frames(n)):
+                raise ValueError(f"noise {b} has shape {tuple(noises[b].shape)}, clip {b} has [{self.D}, {self.frames(n)}] latents")
+            lens.append(n)
+        for b, w in enumerate(waves):                            # shapes first: they are checked wherever the clips live
+            if not w.is_cuda:
+                raise ValueError(f"clip {b} is not on the device (there is no CPU path)")
+        return lens
+
+    @torch.no_grad()
+    def encode_ragged(self, waves, noises=None, generator: torch.Generator = None):
+        """Clips of different lengths (a list of mono [n] / [1, n] device tensors) as ONE zero-padded batch ->
+        [(z_b, mu_b, logs_b)], each [D, frames(len_b)] fp32: the values of encode(clip_b[None, None]), bit for bit - a member of
+        len_b samples has _down(len_b, s) rows after each stride-s conv, floors included, and every layer masks the rows beyond
+        (see _run).  noises[b] [D, frames(len_b)] stands for the reference's randn draw; with a generator instead, one
+        [B, T', D] draw is made and each member uses its own rows of it."""
+        lens = self.check_ragged_args(waves, noises)
+        B, T, D, dev = len(waves), max(lens), self.D, self.dev
+        audio = torch.zeros(B, 1, T, dtype=torch.float32, device=dev)
+        for b, w in enumerate(waves):
+            audio[b, 0, :lens[b]] = w.reshape(-1).to(dev, torch.float32)
+        Tf = [self.frames(n) for n in lens]
+        noise_t = None
+        if noises is not None:
+            noise_t = torch.zeros(B, max(Tf), D, dtype=torch.float32, device=dev)
+            for b, nz in enumerate(noises):
+                noise_t[b, :Tf[b]] = nz.to(dev, torch.float32).t()
+        zt, mt, lt = self._run(audio, B, T, noise_t, generator, lens=lens)
+        return [tuple(src[b, :Tf[b]].t().contiguous() for src in (zt, mt, lt)) for b in range(B)]

@@ -47,8 +47,10 @@ def fade_in_out(fade_in, fade_out, window):
 class TtsEngine:
     def __init__(self, llm_sd, flow_sd, dac_sd, dtype=BF16, device="cuda", max_batch=1, max_ctx=2048,
                  dac_rates=(5, 4, 4, 3, 2), use_graphs=True, attn="bf16", wplanes=False, s3tok_sd=None, dacenc_sd=None,
-                 dacenc_rates=(2, 3, 4, 4, 5)):
-        """wplanes (split build only): the weight-plane mode for checkpoints whose weights are NOT bf16-representable - what the
+                 dacenc_rates=(2, 3, 4, 4, 5), dacenc_fused=False):
+        """dacenc_fused: the DAC-VAE encoder runs the ResidualUnits of its 64- and 128-channel stages as one kernel each
+        (DacEncoderEngine(fuse_ru=True)); off by default, which keeps the prompt latents' bits.
+        wplanes (split build only): the weight-plane mode for checkpoints whose weights are NOT bf16-representable - what the
         reference's loaders hand over (fp32 llm.pt / flow.pt, cli/model.py:67-75; trained weight norms, dac-vae/inference.py:42-46).
         Every GEMM weight is carried as bf16 planes of its fp32 value (3 in the LM, 2 in the flow and the DAC: include/mmx_hip.h
         MMX_X3W / MMX_X2W) and the products keep every term above the last kept bit, so ids identical / waveform <= 1e-3 hold on
@@ -73,6 +75,7 @@ class TtsEngine:
         # zero-shot prompts from a raw clip (prompt_from_audio): the S3 speech tokenizer and the DAC-VAE encoder, built on first use
         self._s3tok_sd, self._dacenc_sd, self._dacenc_rates = s3tok_sd, dacenc_sd, list(dacenc_rates)
         self._s3tok = self._dacenc = None
+        self.dacenc_fused = bool(dacenc_fused)
         # tts_batch's cost model of its own stages (ms): a decode step beside the flow; a flow group = group_ms + frame_ms per frame.
         # Initial values: what _refit_sched measures for this build on one MI355X on the config-4 share (it re-measures them in
         # every call: self.sched_fit; sched_adapt lets the model follow the fit)
@@ -203,7 +206,8 @@ class TtsEngine:
             if self._dacenc_sd is None:
                 raise RuntimeError("prompt_from_audio needs the DAC-VAE encoder: pass dacenc_sd (encoder.* and en_conv_post.* weights)")
             from .dac import DacEncoderEngine
-            self._dacenc = DacEncoderEngine(self._dacenc_sd, self._dacenc_rates, dtype=self.dtype, device=self.dev)
+            self._dacenc = DacEncoderEngine(self._dacenc_sd, self._dacenc_rates, dtype=self.dtype, device=self.dev,
+                                            fuse_ru=self.dacenc_fused)
         return self._dacenc
 
     @torch.no_grad()
@@ -218,6 +222,10 @@ class TtsEngine:
         w24 = wave24k.to(self.dev, torch.float32).reshape(1, 1, -1)
         tok = self.s3tok.tokenize([wave16k.to(self.dev)])[0]
         z = self.dacenc.encode(torch.clamp(w24, -1.0, 1.0), noise=noise, generator=generator)[0]          # [1, 80, T']
+        return self._prompt_dict(tok, z, w24, prompt_text)
+
+    def _prompt_dict(self, tok, z, w24, prompt_text):
+        """The dict of prompt_from_audio from a clip's speech tokens [n], prompt latents z [1, 80, T'] and 24 kHz samples."""
         token_len = min(z.shape[2] // 2, tok.numel())
         tok = tok[:token_len].to(torch.long).reshape(1, -1)
         out = {"llm_prompt_speech_token": tok, "flow_prompt_speech_token": tok,
@@ -240,6 +248,47 @@ class TtsEngine:
         w16 = Resample(sample_rate, 16000)(w)
         w24 = Resample(16000, SAMPLE_RATE)(w16) if via_16k else Resample(sample_rate, SAMPLE_RATE)(w)
         return self.prompt_from_audio(w16, w24, prompt_text, noise, generator)
+
+    @torch.no_grad()
+    def prompts_from_clips(self, waves, sample_rates, prompt_texts=None, noises=None, generator=None, via_16k=True) -> List[dict]:
+        """prompt_from_clip for a list of recordings (mono [n] / [1, n]; sample_rates: one rate or one per clip) with the batched
+        stages run once: the clips that share a rate go through ONE resample launch per target rate (mmx.resample.resample),
+        all of them through ONE speech-tokenizer batch and ONE DAC-VAE encode (DacEncoderEngine.encode_ragged); the speaker
+        embedding stays one reference_embedding per clip.  Entry i is the dict prompt_from_clip(waves[i], ...) returns, bit for
+        bit where noises[i] [80, frames] is given (a `generator` instead gives one draw for the batch, each clip its own rows)."""
+        from .resample import resample as resample_clips
+        n = len(waves)
+        rates = [int(sample_rates)] * n if isinstance(sample_rates, (int, float)) else [int(r) for r in sample_rates]
+        if len(rates) != n or (prompt_texts is not None and len(prompt_texts) != n) or (noises is not None and len(noises) != n):
+            raise ValueError("prompts_from_clips: sample_rates, prompt_texts and noises are per clip")
+        if n == 0:
+            return []
+        ws = [w.to(self.dev, torch.float32).reshape(-1) for w in waves]
+
+        def by_rate(clips, src_rates, new):
+            out = [None] * n
+            for r in sorted(set(src_rates)):
+                idx = [i for i in range(n) if src_rates[i] == r]
+                for i, o in zip(idx, resample_clips([clips[i] for i in idx], r, new)):
+                    out[i] = o
+            return out
+        w16 = by_rate(ws, rates, 16000)
+        w24 = by_rate(w16, [16000] * n, SAMPLE_RATE) if via_16k else by_rate(ws, rates, SAMPLE_RATE)
+        toks = self.s3tok.tokenize(w16)
+        lat = self.dacenc.encode_ragged([torch.clamp(w, -1.0, 1.0) for w in w24], noises=noises, generator=generator)
+        return [self._prompt_dict(toks[i], lat[i][0][None], w24[i].reshape(1, 1, -1), _own(prompt_texts, i)) for i in range(n)]
+
+    @staticmethod
+    def batch_prompt_args(prompts) -> dict:
+        """A list of prompt dicts (prompts_from_clips / prompt_from_clip / prompt_from_audio) -> the per-utterance keyword lists
+        tts_batch takes: eng.tts_batch(texts, **eng.batch_prompt_args(ps)).  flow_embeddings is left out when no prompt has one
+        (a flow without its speaker encoder: pass flow_embeddings= beside it)."""
+        col = lambda k: [p.get(k) for p in prompts]
+        out = {"prompt_texts": col("prompt_text"), "llm_prompt_speech_tokens": col("llm_prompt_speech_token"),
+               "flow_prompt_speech_tokens": col("flow_prompt_speech_token"), "prompt_speech_feats": col("prompt_speech_feat")}
+        if any("flow_embedding" in p for p in prompts):
+            out["flow_embeddings"] = col("flow_embedding")
+        return out
 
     @torch.no_grad()
     def voice_conversion(self, source_wave, source_rate, flow_prompt_speech_token, prompt_speech_feat, flow_embedding, speed=1.0,
