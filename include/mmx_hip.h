@@ -298,7 +298,8 @@ int mmx_skinny_gemm(const void* x, int x_dtype, int64_t ldx, int B, int K, int N
  *   epi 1: SwiGLU of [gate tile | up tile] pairs, written as planes xs_out of width N (the down projection's operand);
  *   epi 2: out[b][n] += acc (+ bias) in place (the residual stream); if xs_out: planes of out * gamma_next; if ssq_out:
  *          the per-tile sums of squares of out.
- *   tiles_per_wg (1 | 2): 16-column tiles a workgroup produces from ONE pass over xs (8 waves = 8 k slices).
+ *   tiles_per_wg (1 | 2; MMX_X3W, three weight planes in registers: 1 only): 16-column tiles a workgroup produces from ONE pass
+ *   over xs (8 waves = 8 k slices).
  *   ksplit (1, or > 1 with epi 2): K is also cut into `ksplit` slices across workgroups; partial tiles go through
  *   `part` (>= ksplit * ceil(N/16) * ceil(B/16)*4 * 64 floats) and are summed in slice order by the workgroup that
  *   takes the last ticket of its tile (`tickets`: ceil(N/16) int32, zero before the first launch; left zero).  Launches
@@ -326,13 +327,20 @@ int mmx_paged_attn(const void* q, int64_t ldq, int64_t q_bs, int B, int rows, in
 /* Single-token decode: RoPE(q), RoPE(k_new), KV append and causal GQA attention in ONE launch per layer
  * (same arithmetic as mmx_rope_kv_store + mmx_paged_attn with rows = 1).  qkv fp32 [B][ldqkv], out T [B][ldo].
  * rope_tab (optional, fp32 [max_pos][D] = cos | sin per position, as HF's rotary embedding computes them) replaces
- * the in-kernel cosf/sinf of pos * inv_freq.  out_packed: bit 0 = write out in the MMX_OUT_PACKED order (K = Hq*D);
- * bit 1 = use the one-workgroup-per-query-head kernel even where the GQA-shared one applies (bf16, page = 16, Hq = 7 Hkv:
- * one workgroup per kv head serves its 7 query heads, Q K^T on the MFMA with the queries split into bf16 hi + lo). */
-/* out_packed bits: 1 = output in the packed A-fragment order of T; 2 = force the per-head kernel; 4 = output as SPLIT PLANES
- * (see mmx_skinny2; dtype MMX_F32 / the split builds only); 8 = output as TWO fp16 planes (MMX_H2, same conditions);
- * 16 = the per-head kernel with ONE query head per workgroup at every batch size (default: from B * Hq > 256 on, two heads share a
- * workgroup's K / V reads; same results bit for bit). */
+ * the in-kernel cosf/sinf of pos * inv_freq.
+ * out_packed: an OR of the MMX_DA_* switches below; any other bit is an error.
+ *   MMX_DA_PACKED   out in the packed A-fragment order of T (MMX_OUT_PACKED, K = Hq*D) instead of row-major.
+ *   MMX_DA_PER_HEAD the per-query-head kernel even where the GQA-shared one applies (bf16, page = 16, Hq = 7 Hkv: one workgroup per
+ *                   kv head serves its 7 query heads, Q K^T on the MFMA with the queries split into bf16 hi + lo).
+ *   MMX_DA_SPLIT    out as SPLIT PLANES, three bf16 terms (see mmx_skinny2); dtype MMX_F32 / the split builds only, without MMX_DA_PACKED.
+ *   MMX_DA_H2       out as TWO fp16 planes (MMX_H2); same conditions, and not together with MMX_DA_SPLIT.
+ *   MMX_DA_ONE_HEAD the per-head kernel with ONE query head per workgroup at every batch size (default: from B * Hq > 256 on, two
+ *                   heads share a workgroup's K / V reads; same results bit for bit). */
+#define MMX_DA_PACKED 1
+#define MMX_DA_PER_HEAD 2
+#define MMX_DA_SPLIT 4
+#define MMX_DA_H2 8
+#define MMX_DA_ONE_HEAD 16
 int mmx_decode_attn(const float* qkv, int64_t ldqkv, int B, int Hq, int Hkv, int D, const float* inv_freq,
                     const float* rope_tab, const int32_t* pos, void* kc, void* vc, const int32_t* block_table, int max_pages, int page,
                     float scale, void* out, int64_t ldo, int dtype, int out_packed, hipStream_t stream);

@@ -121,20 +121,13 @@ extern "C" int mmx_attn_dense(const void* q, int64_t ldq, int64_t q_bs, const vo
     size_t lds = (size_t)(2 * 8 * 64 + 8 + 8 * (size_t)Tk) * 4;
     MMX_CHECK_ARG(lds <= 160 * 1024);
     dim3 grid((Tq - q_begin + 7) / 8, H, B);
-    // 8 score rows of Tk floats: above 64 KB from Tk = 1920
-    if (dtype == MMX_BF16) MMX_LDS_OPT_IN(attn_dense_kernel<bf16_t>, lds);
-    else if (dtype == MMX_F32) MMX_LDS_OPT_IN(attn_dense_kernel<float>, lds);
-    if (dtype == MMX_BF16)
-        hipLaunchKernelGGL(attn_dense_kernel<bf16_t>, grid, dim3(256), lds, stream, (const bf16_t*)q, ldq, q_bs, (const bf16_t*)k, ldk, k_bs,
-                           (const bf16_t*)v, ldv, v_bs, (bf16_t*)out, ldo, o_bs, H, Tq, Tk, scale, keymask, km_bs, chunk,
-                           (const bf16_t*)pos, ldp, pos_u, pos_v, hs, q_begin);
-    else if (dtype == MMX_F32)
-        hipLaunchKernelGGL(attn_dense_kernel<float>, grid, dim3(256), lds, stream, (const float*)q, ldq, q_bs, (const float*)k, ldk, k_bs,
-                           (const float*)v, ldv, v_bs, (float*)out, ldo, o_bs, H, Tq, Tk, scale, keymask, km_bs, chunk,
-                           (const float*)pos, ldp, pos_u, pos_v, hs, q_begin);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        using T = decltype(el);
+        MMX_LDS_OPT_IN(attn_dense_kernel<T>, lds);     // 8 score rows of Tk floats: above 64 KB from Tk = 1920
+        hipLaunchKernelGGL(attn_dense_kernel<T>, grid, dim3(256), lds, stream, (const T*)q, ldq, q_bs, (const T*)k, ldk, k_bs, (const T*)v, ldv, v_bs,
+                           (T*)out, ldo, o_bs, H, Tq, Tk, scale, keymask, km_bs, chunk, (const T*)pos, ldp, pos_u, pos_v, hs, q_begin);
+        return launch_status();
+    });
 }
 
 // ------------------------------------------------------------------------------------------ flash (bf16, D = 64)

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/mmx_hip.h"
 
 // MMX_LAB = 1 (csrc/Makefile, target lab): the measurement build libmmx_hip_lab.so of the SAME sources - shader-clock stamps at
 // the phase boundaries of the decode projections and of the fused estimator tail, switched on through the two mmx_lab_* entry
@@ -53,6 +54,16 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
     bf16x2_t v = __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t);
     return __builtin_bit_cast(unsigned, v);
 }
+
+// Entry points whose kernel is a template over the activation storage type: f(T{}) with T = bf16_t / float for MMX_BF16 / MMX_F32,
+// any other code is MMX_EARG.  f launches and returns a status (launch_status(), or an earlier MMX_EARG).
+template <typename F>
+inline int dispatch_dtype(int dtype, F&& f) {
+    if (dtype == MMX_BF16) return f(bf16_t{});
+    if (dtype == MMX_F32) return f(float{});
+    return MMX_EARG;
+}
+inline int launch_status() { MMX_LAUNCH_CHECK(); return MMX_OK; }
 
 template <typename T> struct Cvt;
 template <> struct Cvt<float> {

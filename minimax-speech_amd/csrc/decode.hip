@@ -29,8 +29,7 @@
 // normal numbers; the epilogue multiplies by 2^-8) and costs two MFMAs per fragment on two thirds of the activation bytes of the
 // three-bf16-plane form; an fp32 checkpoint is two fp16 planes (MMX_H2W: 4 bytes per weight, three MFMAs per fragment) instead
 // of three bf16 planes (MMX_X3W: 6 bytes, six MFMAs).  Range: |activation| < 65504, |weight| < 255.
-#include "common.h"
-#include "../../include/mmx_hip.h"
+#include "act_layout.h"
 
 namespace {
 
@@ -44,27 +43,6 @@ __device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_lo
 constexpr unsigned OOB = 0x80000000u;                  // a buffer offset outside every descriptor below: the load returns 0
 constexpr int SSQ_SLOTS = 64;                          // tile slots per row of a sum-of-squares table
 
-// element index inside ONE plane of the element (row, col) of an activation with nkb k-blocks
-__device__ __forceinline__ int plane_index(int row, int col, int nkb) {
-    return (((((row >> 4) * nkb + (col >> 5)) << 6) + (((col & 31) >> 3) << 4) + (row & 15)) << 3) + (col & 7);
-}
-// v -> NS bf16 terms (NS = 3: hi + mid + lo = v; NS = 1, the bf16 build: bf16(v)) at `idx` of planes `ps` elements apart;
-// F16: NS fp16 terms (round to nearest each; the remainder of a rounded fp32 value is exact in fp32)
-template <int NS, bool F16 = false>
-__device__ __forceinline__ void store_split(bf16_t* planes, int ps, int idx, float v) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        if constexpr (F16) {
-            const _Float16 h = (_Float16)v;
-            planes[s * ps + idx] = __builtin_bit_cast(unsigned short, h);
-            v -= (float)h;
-        } else {
-            const bf16_t h = f2bf(v);
-            planes[s * ps + idx] = h;
-            v -= bf2f(h);
-        }
-    }
-}
 template <bool F16>
 __device__ __forceinline__ float4_t mma16(u32x4_t a, u32x4_t b, float4_t c) {
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, a), __builtin_bit_cast(half8_t, b), c, 0, 0, 0);
@@ -280,13 +258,13 @@ __global__ __launch_bounds__(512) void skinny3_kernel(Skinny3Args a) {
         const bool ok = tile < ntiles && row < a.B && ncol < a.N;
         if constexpr (EPI == 1) {
             const float gte = sum[k][0] * sc, up = sum[k][1] * sc;
-            if (ok) store_split<NS, F16>(a.xs_out, ps_out, plane_index(row, ncol, nkb_out), gte / (1.f + expf(-gte)) * up);
+            if (ok) store_split<NS, F16>(a.xs_out, ps_out, act_index<8, int>(row, ncol, nkb_out), gte / (1.f + expf(-gte)) * up);
         } else {
             float vv = sum[k][0] * sc + pre_bias[k];
             if constexpr (EPI == 2) vv += pre_res[k];
             if (ok) a.out[(long)row * a.ldo + ncol] = vv;
             if constexpr (EPI == 2) {
-                if (ok && a.xs_out) store_split<NS, F16>(a.xs_out, ps_out, plane_index(row, ncol, nkb_out), vv * pre_gn[k]);
+                if (ok && a.xs_out) store_split<NS, F16>(a.xs_out, ps_out, act_index<8, int>(row, ncol, nkb_out), vv * pre_gn[k]);
                 if (a.ssq_out) {                       // this tile's share of the row's sum of squares: over its 16 columns
                     const float q = group16_sum(ok ? vv * vv : 0.f);
                     if (l16 == 0 && tile < ntiles) a.ssq_out[row * SSQ_SLOTS + tile] = q;
@@ -308,6 +286,33 @@ int launch(const Skinny3Args& a, int J, hipStream_t s) {
     return MMX_OK;
 }
 
+// The forms of mmx_skinny2: one row per (dtype, MT, TW) with its three epilogues; a request without a row is MMX_EARG.
+// dtype -> (activation planes NS, weight planes NWP, fp16): X3 (3, 1), X3W (3, 3), H2 (2, 1, fp16), H2W (2, 2, fp16), BF16 (1, 1).
+// KPW is 4 in every form (K <= 1024: <= 4 k-blocks per wave; K = 4864 over 8 slices: <= 3); it stays a template argument of
+// the kernel, whose names profiles/*.csv and tools/check_resources.py key on.
+constexpr int SKINNY2_KPW = 4;
+struct Skinny2Form {
+    int dtype, mt, tw;
+    int (*launch[3])(const Skinny3Args&, int, hipStream_t);      // by epi
+};
+template <int DT, int MT, int TW>
+constexpr Skinny2Form s2() {
+    constexpr bool F16 = DT == MMX_H2 || DT == MMX_H2W;
+    constexpr int KPW = SKINNY2_KPW, NS = DT == MMX_BF16 ? 1 : F16 ? 2 : 3, NWP = DT == MMX_X3W ? 3 : DT == MMX_H2W ? 2 : 1;
+    return {DT, MT, TW, {launch<MT, TW, KPW, 0, NS, NWP, F16>, launch<MT, TW, KPW, 1, NS, NWP, F16>, launch<MT, TW, KPW, 2, NS, NWP, F16>}};
+}
+constexpr Skinny2Form SKINNY2_FORMS[] = {
+    s2<MMX_X3, 1, 1>(), s2<MMX_X3, 2, 1>(), s2<MMX_X3, 1, 2>(), s2<MMX_X3, 2, 2>(), s2<MMX_H2, 1, 1>(), s2<MMX_H2, 2, 1>(), s2<MMX_H2, 1, 2>(), s2<MMX_H2, 2, 2>(),
+    s2<MMX_H2W, 1, 1>(), s2<MMX_H2W, 2, 1>(), s2<MMX_H2W, 1, 2>(), s2<MMX_H2W, 2, 2>(), s2<MMX_BF16, 1, 1>(), s2<MMX_BF16, 2, 1>(), s2<MMX_BF16, 1, 2>(), s2<MMX_BF16, 2, 2>(),
+    s2<MMX_X3W, 1, 1>(), s2<MMX_X3W, 2, 1>(),          // three weight planes in registers: one output tile per workgroup (no TW = 2 row)
+};
+constexpr const Skinny2Form* skinny2_select(int dtype, int mt, int tw) {
+    for (const Skinny2Form& f : SKINNY2_FORMS)
+        if (f.dtype == dtype && f.mt == mt && f.tw == tw) return &f;
+    return nullptr;
+}
+static_assert(skinny2_select(MMX_X3W, 1, 1) && !skinny2_select(MMX_X3W, 1, 2) && !skinny2_select(MMX_X3, 3, 1) && !skinny2_select(MMX_X2, 1, 1));
+
 // x fp32 [B][K] -> residual stream copy h, planes of (x * gamma) and the per-tile sums of squares of x: the form in which
 // the first projection of a decode step wants the sampler's output (the next input embedding)
 template <int NS, bool F16 = false>
@@ -322,7 +327,7 @@ __global__ __launch_bounds__(256) void decode_prep_kernel(const float* __restric
         if (col < K) {
             v = x[(long)row * ldx + col];
             if (h) h[(long)row * ldh + col] = v;
-            store_split<NS, F16>(xs, ps, plane_index(row, col, nkb), v * (gamma ? gamma[col] : 1.f));
+            store_split<NS, F16>(xs, ps, act_index<8, int>(row, col, nkb), v * (gamma ? gamma[col] : 1.f));
         }
         const float q = group16_sum(v * v);
         if ((t0 & 15) == 0) ssq[row * SSQ_SLOTS + tile] = q;           // tiles beyond K / 16 get 0
@@ -347,16 +352,16 @@ extern "C" int mmx_skinny2(const void* xs, int B, int K, int N, const void* wp, 
                            int epi, float* out, int64_t ldo, void* xs_out, const float* gamma_next, float* ssq_out,
                            int tiles_per_wg, int ksplit, float* part, int64_t part_floats, int32_t* tickets, int dtype,
                            hipStream_t stream) {
-    MMX_CHECK_ARG(xs && wp && B > 0 && B <= 32 && K > 0 && K % 32 == 0 && N > 0 &&
-                  (dtype == MMX_X3 || dtype == MMX_X3W || dtype == MMX_BF16 || dtype == MMX_H2 || dtype == MMX_H2W));
-    MMX_CHECK_ARG(dtype != MMX_X3W || tiles_per_wg == 1);   // three weight planes in registers: one output tile per workgroup
+    MMX_CHECK_ARG(xs && wp && B > 0 && B <= 32 && K > 0 && K % 32 == 0 && N > 0 && epi >= 0 && epi <= 2);
+    const int nkb = K / 32, ntiles = (N + 15) / 16, mt = (B + 15) / 16;
+    const Skinny2Form* form = skinny2_select(dtype, mt, tiles_per_wg);
+    MMX_CHECK_ARG(form);
     MMX_CHECK_ARG(((uintptr_t)xs % 16) == 0 && ((uintptr_t)wp % 16) == 0 && (!ssq_in || ((uintptr_t)ssq_in % 16) == 0));
     MMX_CHECK_ARG(ksplit >= 1 && ksplit <= 8 && (ksplit == 1 || (epi == 2 && part && tickets)));
     MMX_CHECK_ARG(epi == 1 ? (xs_out != nullptr && N % 32 == 0) : out != nullptr);
     MMX_CHECK_ARG(epi != 2 || !xs_out || N % 32 == 0);
     MMX_CHECK_ARG(epi != 2 || !ssq_out || (N + 15) / 16 <= SSQ_SLOTS);
-    const int nkb = K / 32, ntiles = (N + 15) / 16, mt = (B + 15) / 16;
-    const int per_wave = ((nkb + ksplit - 1) / ksplit + 7) / 8;
+    MMX_CHECK_ARG(((nkb + ksplit - 1) / ksplit + 7) / 8 <= SKINNY2_KPW);      // k-blocks per wave
     MMX_CHECK_ARG(ksplit == 1 || part_floats >= (int64_t)ksplit * ((ntiles + tiles_per_wg - 1) / tiles_per_wg) * tiles_per_wg * mt * 4 * 64);
     // 32-bit buffer offsets: the packed weights and the planes must stay below 2 GiB
     const double plane_bytes = (double)ntiles * (epi == 1 ? 2 : 1) * nkb * 1024.0;
@@ -364,20 +369,7 @@ extern "C" int mmx_skinny2(const void* xs, int B, int K, int N, const void* wp, 
     const bool f16 = dtype == MMX_H2 || dtype == MMX_H2W;
     Skinny3Args a{(const bf16_t*)xs, (const bf16_t*)wp, bias, ssq_in, out, (bf16_t*)xs_out, gamma_next, ssq_out, part, tickets,
                   ldo, B, K, N, ntiles, (nkb + ksplit - 1) / ksplit, eps, (unsigned)plane_bytes, f16 ? 1.0f / H2_WSCALE : 1.0f};
-#define GO(MT, TW, KPW, EPI) do { if (dtype == MMX_X3) return launch<MT, TW, KPW, EPI, 3>(a, ksplit, stream); \
-                                  if (dtype == MMX_H2) return launch<MT, TW, KPW, EPI, 2, 1, true>(a, ksplit, stream); \
-                                  if (dtype == MMX_H2W) return launch<MT, TW, KPW, EPI, 2, 2, true>(a, ksplit, stream); \
-                                  if (dtype == MMX_X3W) { if constexpr (TW == 1) return launch<MT, 1, KPW, EPI, 3, 3>(a, ksplit, stream); else return MMX_EARG; } \
-                                  return launch<MT, TW, KPW, EPI, 1>(a, ksplit, stream); } while (0)
-#define BY_MT(TW, KPW, EPI) do { if (mt == 1) GO(1, TW, KPW, EPI); else GO(2, TW, KPW, EPI); } while (0)
-    if (per_wave <= 4) {
-        if (epi == 0) { if (tiles_per_wg == 1) BY_MT(1, 4, 0); if (tiles_per_wg == 2) BY_MT(2, 4, 0); }
-        if (epi == 1) { if (tiles_per_wg == 1) BY_MT(1, 4, 1); if (tiles_per_wg == 2) BY_MT(2, 4, 1); }
-        if (epi == 2) { if (tiles_per_wg == 1) BY_MT(1, 4, 2); if (tiles_per_wg == 2) BY_MT(2, 4, 2); }
-    }
-#undef BY_MT
-#undef GO
-    return MMX_EARG;
+    return form->launch[epi](a, ksplit, stream);
 }
 
 #if MMX_LAB

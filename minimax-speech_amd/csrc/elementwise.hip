@@ -1,7 +1,9 @@
 // Row-wise and elementwise kernels of the hot path (all HBM-bound: coalesced rows, wave-shuffle
 // reductions, one pass over the data).  See include/mmx_hip.h for the contracts.
 #include "common.h"
-#include "../../include/mmx_hip.h"
+#include <type_traits>
+
+template <int V> using ic = std::integral_constant<int, V>;
 
 // ---------------------------------------------------------------------------- rownorm
 // one wave per row, the row in registers (C <= 64 * MAXV; 2048 at most: the speech tokenizer's 1280 channels take MAXV = 32).
@@ -60,16 +62,15 @@ extern "C" int mmx_rownorm(const float* x, int64_t ldx, int64_t x_bstride, int r
     MMX_CHECK_ARG(x && gamma && rows > 0 && C > 0 && C <= 2048 && batch > 0 && (out_f32 || out_act));
     dim3 grid((rows + 3) / 4, batch);
     MMX_CHECK_ARG(act == ACT_NONE || act == ACT_MISH);
-#define RN2(T, MV, A) hipLaunchKernelGGL((rownorm_kernel<T, MV, A>), grid, dim3(256), 0, stream, x, ldx, x_bstride, rows, C, \
-        gamma, beta, eps, rms, act, rowmask, rm_bstride, addvec, av_bstride, out_f32, ldo_f, of_bstride, (T*)out_act, ldo_a, oa_bstride)
-#define RN(T, MV) do { if (act == ACT_MISH) RN2(T, MV, ACT_MISH); else RN2(T, MV, ACT_NONE); } while (0)
-    if (dtype == MMX_BF16) { if (C <= 256) RN(bf16_t, 4); else if (C <= 512) RN(bf16_t, 8); else if (C <= 1024) RN(bf16_t, 16); else RN(bf16_t, 32); }
-    else if (dtype == MMX_F32) { if (C <= 256) RN(float, 4); else if (C <= 512) RN(float, 8); else if (C <= 1024) RN(float, 16); else RN(float, 32); }
-    else return MMX_EARG;
-#undef RN
-#undef RN2
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        auto go = [&](auto mv, auto a) {               // MV: values a thread holds (C <= 64 * MV); A: the activation, compile time
+            hipLaunchKernelGGL((rownorm_kernel<decltype(el), mv(), a()>), grid, dim3(256), 0, stream, x, ldx, x_bstride, rows, C, gamma, beta, eps, rms, act,
+                               rowmask, rm_bstride, addvec, av_bstride, out_f32, ldo_f, of_bstride, (decltype(el)*)out_act, ldo_a, oa_bstride);
+            return launch_status();
+        };
+        auto by_c = [&](auto a) { return C <= 256 ? go(ic<4>{}, a) : C <= 512 ? go(ic<8>{}, a) : C <= 1024 ? go(ic<16>{}, a) : go(ic<32>{}, a); };
+        return act == ACT_MISH ? by_c(ic<ACT_MISH>{}) : by_c(ic<ACT_NONE>{});
+    });
 }
 
 // ---------------------------------------------------------------------------- gather rows
@@ -91,13 +92,10 @@ extern "C" int mmx_gather_rows(const int64_t* ids, int n, const float* table, in
                                float* out_f32, int64_t ldo_f, void* out_act, int64_t ldo_a, int dtype, hipStream_t stream) {
     dtype = MMX_ACT_DTYPE(dtype);
     MMX_CHECK_ARG(ids && table && n > 0 && C > 0 && (out_f32 || out_act));
-    if (dtype == MMX_BF16)
-        hipLaunchKernelGGL(gather_rows_kernel<bf16_t>, dim3(n), dim3(256), 0, stream, ids, n, table, C, scale, rowmask, out_f32, ldo_f, (bf16_t*)out_act, ldo_a);
-    else if (dtype == MMX_F32)
-        hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(n), dim3(256), 0, stream, ids, n, table, C, scale, rowmask, out_f32, ldo_f, (float*)out_act, ldo_a);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        hipLaunchKernelGGL(gather_rows_kernel<decltype(el)>, dim3(n), dim3(256), 0, stream, ids, n, table, C, scale, rowmask, out_f32, ldo_f, (decltype(el)*)out_act, ldo_a);
+        return launch_status();
+    });
 }
 
 // ---------------------------------------------------------------------------- copy2d (transposing cast through LDS)
@@ -135,15 +133,13 @@ extern "C" int mmx_copy2d(const void* in, int in_dtype, int64_t ibs, int64_t irs
     out_dtype = MMX_ACT_DTYPE(out_dtype);
     MMX_CHECK_ARG(in && out && rows > 0 && cols > 0 && batch > 0 && rep >= 1);
     dim3 grid((cols + 31) / 32, (rows + 31) / 32, batch);
-#define CP(TI, TO) hipLaunchKernelGGL((copy2d_kernel<TI, TO>), grid, dim3(256), 0, stream, (const TI*)in, ibs, irs, ics, rep, (TO*)out, obs, ors, ocs, rows, cols)
-    if (in_dtype == MMX_F32 && out_dtype == MMX_F32) CP(float, float);
-    else if (in_dtype == MMX_F32 && out_dtype == MMX_BF16) CP(float, bf16_t);
-    else if (in_dtype == MMX_BF16 && out_dtype == MMX_F32) CP(bf16_t, float);
-    else if (in_dtype == MMX_BF16 && out_dtype == MMX_BF16) CP(bf16_t, bf16_t);
-    else return MMX_EARG;
-#undef CP
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(in_dtype, [&](auto ti) {
+        return dispatch_dtype(out_dtype, [&](auto to) {
+            hipLaunchKernelGGL((copy2d_kernel<decltype(ti), decltype(to)>), grid, dim3(256), 0, stream, (const decltype(ti)*)in, ibs, irs, ics, rep,
+                               (decltype(to)*)out, obs, ors, ocs, rows, cols);
+            return launch_status();
+        });
+    });
 }
 
 // ---------------------------------------------------------------------------- estimator input pack / time embedding
@@ -168,11 +164,10 @@ extern "C" int mmx_est_pack(const float* x, int64_t x_bs, int x_mod, const float
     dtype = MMX_ACT_DTYPE(dtype);
     MMX_CHECK_ARG(x && h && B > 0 && T_ > 0 && C > 0 && ldh >= 4 * C && x_mod > 0);
     dim3 grid(T_, B);
-    if (dtype == MMX_BF16) hipLaunchKernelGGL(est_pack_kernel<bf16_t>, grid, dim3(128), 0, stream, x, x_bs, x_mod, mu, spks, cond, T_, C, (bf16_t*)h, ldh);
-    else if (dtype == MMX_F32) hipLaunchKernelGGL(est_pack_kernel<float>, grid, dim3(128), 0, stream, x, x_bs, x_mod, mu, spks, cond, T_, C, (float*)h, ldh);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        hipLaunchKernelGGL(est_pack_kernel<decltype(el)>, grid, dim3(128), 0, stream, x, x_bs, x_mod, mu, spks, cond, T_, C, (decltype(el)*)h, ldh);
+        return launch_status();
+    });
 }
 
 template <typename T>
@@ -189,11 +184,10 @@ __global__ void sinusoidal_kernel(const float* __restrict__ t, int dim, float sc
 extern "C" int mmx_sinusoidal_emb(const float* t, int B, int dim, float scale, void* out, int dtype, hipStream_t stream) {
     dtype = MMX_ACT_DTYPE(dtype);
     MMX_CHECK_ARG(t && out && B > 0 && dim >= 4 && dim % 2 == 0);
-    if (dtype == MMX_BF16) hipLaunchKernelGGL(sinusoidal_kernel<bf16_t>, dim3(B), dim3(128), 0, stream, t, dim, scale, (bf16_t*)out);
-    else if (dtype == MMX_F32) hipLaunchKernelGGL(sinusoidal_kernel<float>, dim3(B), dim3(128), 0, stream, t, dim, scale, (float*)out);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        hipLaunchKernelGGL(sinusoidal_kernel<decltype(el)>, dim3(B), dim3(128), 0, stream, t, dim, scale, (decltype(el)*)out);
+        return launch_status();
+    });
 }
 
 __global__ void cfg_euler_kernel(float* __restrict__ x, const float* __restrict__ dc, const float* __restrict__ du,
@@ -248,15 +242,11 @@ extern "C" int mmx_conv_cout1_tanh(const void* act, int64_t a_bs, int T_, int C,
     size_t lds = (size_t)k * C * 4 + (size_t)(256 + k - 1) * C * esz;
     MMX_CHECK_ARG(lds <= 160 * 1024);
     // above 64 KB the launch needs the per-function opt-in, as the GEMM's larger tiles do (fp32 / split builds from C = 64 at k = 7)
-    if (dtype == MMX_BF16) {
-        MMX_LDS_OPT_IN(conv_cout1_kernel<bf16_t>, lds);
-        hipLaunchKernelGGL(conv_cout1_kernel<bf16_t>, grid, dim3(256), lds, stream, (const bf16_t*)act, a_bs, T_, C, k, w, bias, slope, use_tanh, out, o_bs);
-    } else if (dtype == MMX_F32) {
-        MMX_LDS_OPT_IN(conv_cout1_kernel<float>, lds);
-        hipLaunchKernelGGL(conv_cout1_kernel<float>, grid, dim3(256), lds, stream, (const float*)act, a_bs, T_, C, k, w, bias, slope, use_tanh, out, o_bs);
-    } else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        MMX_LDS_OPT_IN(conv_cout1_kernel<decltype(el)>, lds);
+        hipLaunchKernelGGL(conv_cout1_kernel<decltype(el)>, grid, dim3(256), lds, stream, (const decltype(el)*)act, a_bs, T_, C, k, w, bias, slope, use_tanh, out, o_bs);
+        return launch_status();
+    });
 }
 
 // ---------------------------------------------------------------------------- DAC-VAE encoder head / VAE sampling
@@ -308,11 +298,10 @@ extern "C" int mmx_conv_cin1(const float* x, int64_t x_bs, int T_, int C, int k,
     MMX_CHECK_ARG(x && w && (out_f32 || out_act) && T_ > 0 && C > 0 && C % 8 == 0 && k > 0 && (k & 1) && batch > 0);
     dim3 grid((T_ + 255) / 256, batch);
     size_t lds = (size_t)(256 + k - 1 + C * k) * 4;
-    if (dtype == MMX_BF16) hipLaunchKernelGGL(conv_cin1_kernel<bf16_t>, grid, dim3(256), lds, stream, x, x_bs, T_, C, k, w, bias, slope, alpha, out_f32, (bf16_t*)out_act);
-    else if (dtype == MMX_F32) hipLaunchKernelGGL(conv_cin1_kernel<float>, grid, dim3(256), lds, stream, x, x_bs, T_, C, k, w, bias, slope, alpha, out_f32, (float*)out_act);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        hipLaunchKernelGGL(conv_cin1_kernel<decltype(el)>, grid, dim3(256), lds, stream, x, x_bs, T_, C, k, w, bias, slope, alpha, out_f32, (decltype(el)*)out_act);
+        return launch_status();
+    });
 }
 
 __global__ void vae_sample_kernel(const float* __restrict__ ml, const float* __restrict__ noise, long n, int D,
@@ -470,11 +459,10 @@ extern "C" int mmx_swiglu(const float* gu, int64_t ldgu, int rows, int I, void* 
     dtype = MMX_ACT_DTYPE(dtype);
     MMX_CHECK_ARG(gu && out && rows > 0 && I > 0);
     dim3 grid((I + 255) / 256, rows);
-    if (dtype == MMX_BF16) hipLaunchKernelGGL(swiglu_kernel<bf16_t>, grid, dim3(256), 0, stream, gu, ldgu, I, (bf16_t*)out, ldo);
-    else if (dtype == MMX_F32) hipLaunchKernelGGL(swiglu_kernel<float>, grid, dim3(256), 0, stream, gu, ldgu, I, (float*)out, ldo);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        hipLaunchKernelGGL(swiglu_kernel<decltype(el)>, grid, dim3(256), 0, stream, gu, ldgu, I, (decltype(el)*)out, ldo);
+        return launch_status();
+    });
 }
 
 // ---------------------------------------------------------------------------- GroupNorm over time-major [B][T][C]
@@ -521,11 +509,10 @@ extern "C" int mmx_groupnorm(const float* x, int B, int T_, int C, int groups, c
     MMX_CHECK_ARG(x && gamma && beta && out && B > 0 && T_ > 0 && C > 0 && groups > 0 && C % groups == 0);
     MMX_CHECK_ARG(act == ACT_NONE || act == ACT_MISH);
     dim3 grid(groups, B);
-    if (dtype == MMX_BF16) hipLaunchKernelGGL(groupnorm_kernel<bf16_t>, grid, dim3(256), 0, stream, x, T_, C, C / groups, gamma, beta, eps, act, rowmask, (bf16_t*)out);
-    else if (dtype == MMX_F32) hipLaunchKernelGGL(groupnorm_kernel<float>, grid, dim3(256), 0, stream, x, T_, C, C / groups, gamma, beta, eps, act, rowmask, (float*)out);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        hipLaunchKernelGGL(groupnorm_kernel<decltype(el)>, grid, dim3(256), 0, stream, x, T_, C, C / groups, gamma, beta, eps, act, rowmask, (decltype(el)*)out);
+        return launch_status();
+    });
 }
 
 // ---------------------------------------------------------------------------- elementwise activation * row mask
@@ -546,11 +533,10 @@ extern "C" int mmx_act_rows(const float* x, int64_t rows, int C, int act, const 
     MMX_CHECK_ARG(x && rows > 0 && C > 0 && (out_f32 || out_act) && act >= ACT_NONE && act <= ACT_TANH);
     const long n = rows * C;
     const unsigned grid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    if (dtype == MMX_BF16) hipLaunchKernelGGL(act_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, x, n, C, act, rowmask, out_f32, (bf16_t*)out_act);
-    else if (dtype == MMX_F32) hipLaunchKernelGGL(act_rows_kernel<float>, dim3(grid), dim3(256), 0, stream, x, n, C, act, rowmask, out_f32, (float*)out_act);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        hipLaunchKernelGGL(act_rows_kernel<decltype(el)>, dim3(grid), dim3(256), 0, stream, x, n, C, act, rowmask, out_f32, (decltype(el)*)out_act);
+        return launch_status();
+    });
 }
 
 extern "C" int mmx_abi_version(void) { return 10; }

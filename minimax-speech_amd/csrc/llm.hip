@@ -5,8 +5,8 @@
 // the <= 64 activation rows ride the A operand of v_mfma_f32_16x16x32_bf16, K is split across the waves
 // of a workgroup and reduced through LDS (deterministic: no atomics), RMSNorm is folded into the
 // projection (its weight into Wp at pack time, 1/rms as a per-row scale computed from the same x loads).
-#include "common.h"
-#include "../../include/mmx_hip.h"
+#include "act_layout.h"
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------ pack
 // bf16: Wp[tile][kt][lane][8]  = W[row(tile, lane&15)][kt*32 + 8*(lane>>4) + j] * kscale[k]
@@ -43,11 +43,11 @@ extern "C" int mmx_pack_skinny(const void* w, int64_t ldw, int N, int K, const f
     MMX_CHECK_ARG(w && wp && N > 0 && K > 0 && K % 32 == 0);
     MMX_CHECK_ARG(interleave_half == 0 || (N == 2 * interleave_half && interleave_half % 16 == 0));
     if (dtype == MMX_X2 || dtype == MMX_X3) { MMX_CHECK_ARG(!kscale); dtype = MMX_BF16; }   // split build: exact bf16 weights
-    if (dtype == MMX_BF16) hipLaunchKernelGGL(pack_skinny_kernel<bf16_t>, dim3(2048), dim3(256), 0, stream, (const bf16_t*)w, ldw, N, K, kscale, interleave_half, (bf16_t*)wp);
-    else if (dtype == MMX_F32) hipLaunchKernelGGL(pack_skinny_kernel<float>, dim3(2048), dim3(256), 0, stream, (const float*)w, ldw, N, K, kscale, interleave_half, (float*)wp);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        using T = decltype(el);
+        hipLaunchKernelGGL(pack_skinny_kernel<T>, dim3(2048), dim3(256), 0, stream, (const T*)w, ldw, N, K, kscale, interleave_half, (T*)wp);
+        return launch_status();
+    });
 }
 
 // ------------------------------------------------------------------------------------------ packed activations
@@ -57,11 +57,11 @@ extern "C" int mmx_pack_skinny(const void* w, int64_t ldw, int N, int K, const f
 // workgroup re-reads the whole activation matrix from L2, and at batch 32 those reads cost more than the weight
 // stream (tools/skinny_lab.hip: 10.6 -> 8.6 us gate/up, 15.2 -> 10.7 us down).  Producers (the GEMM epilogues
 // and the decode attention) write this layout directly.  At batch <= 8 row-major wins (only the valid rows move).
+// (csrc/act_layout.h states the order; this file indexes it in `long`, as it always did)
 template <typename T>
 __device__ __forceinline__ long act_packed_index(int row, int col, int K) {
-    constexpr int E = sizeof(T) == 2 ? 8 : 4, KB = 4 * E;
-    const int kb = col / KB, g = (col % KB) / E, j = col % E;
-    return ((((long)(row >> 4) * (K / KB) + kb) * 64) + g * 16 + (row & 15)) * E + j;
+    constexpr int E = sizeof(T) == 2 ? 8 : 4;
+    return act_index<E, long>(row, col, K / (4 * E));
 }
 
 // ------------------------------------------------------------------------------------------ skinny GEMM
@@ -69,10 +69,11 @@ __device__ __forceinline__ long act_packed_index(int row, int col, int K) {
 // The whole problem is latency bound (a projection is 1.6 - 17 MB, a single HBM round trip is ~1-2 us), so
 // bandwidth comes from bytes in flight: every wave issues ALL the weight loads of its k slice (<= KS k-blocks,
 // 1 KiB per wave-instruction) back to back into registers before the first MFMA, and the k split is chosen so
-// that a slice fits (skinny_launch_mt below).
+// that a slice fits (skinny_launch below).
 // NS > 1 (MMX_X2 / MMX_X3): bf16 weights, fp32 activations split into NS bf16 terms per product (see csrc/gemm.hip);
 // the RMSNorm gain is then NOT folded into the weights (they must stay the checkpoint's bf16 values): kgamma [K]
 // multiplies the activations before the split.
+constexpr int skinny_ks(int mt) { return mt == 1 ? 10 : (mt == 2 ? 7 : 4); }   // k-blocks a wave keeps in flight (register budget)
 template <typename T, typename TX, int MT, int EPI, int KS, bool XPK, bool OPK, int NS = 1>
 __global__ __launch_bounds__(512) void skinny_gemm_kernel(const TX* __restrict__ x, long ldx, int B, int K, int N,
                                    const T* __restrict__ wp, const float* __restrict__ bias, int rs, float eps,
@@ -311,102 +312,91 @@ __global__ __launch_bounds__(512) void skinny_gemm_kernel(const TX* __restrict__
     }
 }
 
-template <typename T, typename TX, int EPI, bool XPK, bool OPK, int NS = 1>
-static int skinny_launch_mt(const void* x, int64_t ldx, int B, int K, int N, const void* wp, const float* bias, int rs,
-                            float eps, float* outf, int64_t ldo_f, void* outa, int64_t ldo_a, hipStream_t s,
-                            const float* kgamma = nullptr) {
-    constexpr int KB = sizeof(T) == 2 ? 32 : 16;
-    const int ntiles = (N + 15) / 16;                  // for EPI==1, N is the activation width I
-    const int nkb = K / KB;
+// Host side: ONE launcher template, a table with one row per (weight type, activation type, epilogue, x layout, out layout, NS) -
+// each row is the four MT instantiations of its kernel - and a constexpr selection from the request to a row, none = MMX_EARG.
+struct SkinnyArgs {
+    const void* x; int64_t ldx; int B, K, N; const void* wp; const float* bias; int rs; float eps;
+    float* outf; int64_t ldo_f; void* outa; int64_t ldo_a; const float* kgamma;
+};
+template <typename T, typename TX, int EPI, bool XPK, bool OPK, int NS>
+static int skinny_launch(const SkinnyArgs& a, hipStream_t s) {
+    constexpr int KB = sizeof(T) == 2 ? 32 : 16, NB = EPI == 1 ? 2 : 1;
+    const int ntiles = (a.N + 15) / 16;                // for EPI==1, N is the activation width I
+    const int nkb = a.K / KB, mt = (a.B + 15) / 16;
     // smallest power-of-two k split (<= 8 waves = 512 threads per workgroup, so a wave may use 256 VGPRs) whose
-    // slice fits KS blocks; a longer slice is walked in chunks of KS
-    const int mt = (B + 15) / 16;
-    const int KSr = mt == 1 ? 10 : (mt == 2 ? 7 : 4);  // k-blocks a wave keeps in flight (register budget)
+    // slice fits skinny_ks(mt) blocks; a longer slice is walked in chunks of that many
     int ksplit = 1;
-    while (ksplit < 8 && (nkb + ksplit - 1) / ksplit > KSr) ksplit *= 2;
+    while (ksplit < 8 && (nkb + ksplit - 1) / ksplit > skinny_ks(mt)) ksplit *= 2;
     int waves = ksplit >= 4 ? ksplit : 4;
     // batch > 16 and a wide N (gate/up): two tiles per workgroup - the waves of the same k slice then share their
     // activation fragments through the L1 (tools/skinny_lab.hip: 9.06 -> 8.55 us)
     if (mt >= 2 && ksplit <= 4 && ntiles >= 256) waves = 8;
-    int tpb = waves / ksplit;
-    dim3 grid((ntiles + tpb - 1) / tpb), block(waves * 64);
-    constexpr int NB = EPI == 1 ? 2 : 1;
-    size_t lds = ksplit > 1 ? (size_t)waves * (NB * mt * 4 + mt) * 64 * 4 : 0;
-#define SK(MT) hipLaunchKernelGGL((skinny_gemm_kernel<T, TX, MT, EPI, (MT == 1 ? 10 : (MT == 2 ? 7 : 4)), XPK, OPK, NS>), grid, block, lds, s, (const TX*)x, ldx, B, K, N, (const T*)wp, \
-        bias, rs, eps, outf, ldo_f, (T*)outa, ldo_a, ksplit, ntiles, kgamma)
-    switch (mt) {
-        case 1: SK(1); break;
-        case 2: SK(2); break;
-        case 3: SK(3); break;
-        case 4: SK(4); break;
-        default: return MMX_EARG;
-    }
-#undef SK
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    const int tpb = waves / ksplit;
+    const dim3 grid((ntiles + tpb - 1) / tpb), block(waves * 64);
+    const size_t lds = ksplit > 1 ? (size_t)waves * (NB * mt * 4 + mt) * 64 * 4 : 0;
+    auto go = [&](auto mtc) {
+        constexpr int MT = decltype(mtc)::value;
+        hipLaunchKernelGGL((skinny_gemm_kernel<T, TX, MT, EPI, skinny_ks(MT), XPK, OPK, NS>), grid, block, lds, s, (const TX*)a.x, a.ldx, a.B, a.K, a.N,
+                           (const T*)a.wp, a.bias, a.rs, a.eps, a.outf, a.ldo_f, (T*)a.outa, a.ldo_a, ksplit, ntiles, a.kgamma);
+        return launch_status();
+    };
+    using std::integral_constant;
+    return mt == 1 ? go(integral_constant<int, 1>{}) : mt == 2 ? go(integral_constant<int, 2>{}) : mt == 3 ? go(integral_constant<int, 3>{})
+         : mt == 4 ? go(integral_constant<int, 4>{}) : MMX_EARG;
 }
-template <typename T, typename TX, bool XPK, bool OPK>
-static int skinny_launch_epi(int epi, const void* x, int64_t ldx, int B, int K, int N, const void* wp, const float* bias,
-                             int rs, float eps, float* outf, int64_t ldo_f, void* outa, int64_t ldo_a, hipStream_t s) {
-    if (epi == 0) return skinny_launch_mt<T, TX, 0, XPK, OPK>(x, ldx, B, K, N, wp, bias, rs, eps, outf, ldo_f, outa, ldo_a, s);
-    if (epi == 1) return skinny_launch_mt<T, TX, 1, XPK, OPK>(x, ldx, B, K, N, wp, bias, rs, eps, outf, ldo_f, outa, ldo_a, s);
-    if (epi == 2) return skinny_launch_mt<T, TX, 2, XPK, OPK>(x, ldx, B, K, N, wp, bias, rs, eps, outf, ldo_f, outa, ldo_a, s);
-    return MMX_EARG;
+struct SkinnyForm {
+    int dtype, x_dtype, epi, flags;                    // weights (MMX_X2 / MMX_X3: bf16 weights, NS = 2 / 3), activations, epilogue, layouts
+    int (*launch)(const SkinnyArgs&, hipStream_t);
+};
+template <typename T, typename TX, int EPI, int FLAGS = 0, int NS = 1>
+constexpr SkinnyForm sk() {
+    return {NS > 1 ? NS : sizeof(T) == 2 ? MMX_BF16 : MMX_F32, sizeof(TX) == 2 ? MMX_BF16 : MMX_F32, EPI, FLAGS,
+            skinny_launch<T, TX, EPI, (FLAGS & MMX_X_PACKED) != 0, (FLAGS & MMX_OUT_PACKED) != 0, NS>};
 }
+static_assert(MMX_X2 == 2 && MMX_X3 == 3, "the split dtype codes are their NS");
 // the activation layouts are compile-time (a runtime switch inside the unrolled load block cost ~1 us per launch at
-// batch 1); the combinations the decode step uses: row-major, packed x only, packed x and packed out_act
-template <typename T, typename TX>
-static int skinny_launch_layout(int flags, int epi, const void* x, int64_t ldx, int B, int K, int N, const void* wp,
-                                const float* bias, int rs, float eps, float* outf, int64_t ldo_f, void* outa, int64_t ldo_a,
-                                hipStream_t s) {
-    if constexpr (sizeof(T) == sizeof(TX)) {
-        if (flags == (MMX_X_PACKED | MMX_OUT_PACKED))
-            return skinny_launch_epi<T, TX, true, true>(epi, x, ldx, B, K, N, wp, bias, rs, eps, outf, ldo_f, outa, ldo_a, s);
-        if (flags == MMX_X_PACKED)
-            return skinny_launch_epi<T, TX, true, false>(epi, x, ldx, B, K, N, wp, bias, rs, eps, outf, ldo_f, outa, ldo_a, s);
-    }
-    if (flags == 0) return skinny_launch_epi<T, TX, false, false>(epi, x, ldx, B, K, N, wp, bias, rs, eps, outf, ldo_f, outa, ldo_a, s);
-    return MMX_EARG;
+// batch 1); the combinations the decode step uses: row-major, packed x only, packed x and packed out_act (same type only)
+constexpr int XP = MMX_X_PACKED, XOP = MMX_X_PACKED | MMX_OUT_PACKED;
+constexpr SkinnyForm SKINNY_FORMS[] = {
+    sk<bf16_t, bf16_t, 0>(), sk<bf16_t, bf16_t, 1>(), sk<bf16_t, bf16_t, 2>(), sk<bf16_t, bf16_t, 0, XP>(), sk<bf16_t, bf16_t, 1, XP>(), sk<bf16_t, bf16_t, 2, XP>(),
+    sk<bf16_t, bf16_t, 0, XOP>(), sk<bf16_t, bf16_t, 1, XOP>(), sk<bf16_t, bf16_t, 2, XOP>(),
+    sk<float, float, 0>(), sk<float, float, 1>(), sk<float, float, 2>(), sk<float, float, 0, XP>(), sk<float, float, 1, XP>(), sk<float, float, 2, XP>(),
+    sk<float, float, 0, XOP>(), sk<float, float, 1, XOP>(), sk<float, float, 2, XOP>(),
+    sk<bf16_t, float, 0>(), sk<bf16_t, float, 1>(), sk<bf16_t, float, 2>(),                // (with kgamma: the gain on fp32 x, epi 0 / 1)
+    sk<bf16_t, float, 0, 0, 2>(), sk<bf16_t, float, 1, 0, 2>(), sk<bf16_t, float, 2, 0, 2>(),   // split builds
+    sk<bf16_t, float, 0, 0, 3>(), sk<bf16_t, float, 1, 0, 3>(), sk<bf16_t, float, 2, 0, 3>(),
+};
+constexpr const SkinnyForm* skinny_select(int dtype, int x_dtype, int flags, int epi, bool kgamma) {
+    // kgamma outside the split builds: bf16 weights (packed WITHOUT kscale) and fp32 x only - the prompt chunks of the bf16 build,
+    // whose decode step runs on csrc/decode.hip.  Only epi 0 / 1 ever took it; epi 2 with kgamma stays refused.
+    if (kgamma && dtype != MMX_X2 && dtype != MMX_X3 && !(dtype == MMX_BF16 && x_dtype == MMX_F32 && epi != 2)) return nullptr;
+    for (const SkinnyForm& f : SKINNY_FORMS)
+        if (f.dtype == dtype && f.x_dtype == x_dtype && f.flags == flags && f.epi == epi) return &f;
+    return nullptr;
 }
-template <int NS>
-static int skinny_launch_split(int epi, const void* x, int64_t ldx, int B, int K, int N, const void* wp, const float* bias, int rs,
-                               float eps, float* outf, int64_t ldo_f, hipStream_t s, const float* kgamma) {
-    if (epi == 0) return skinny_launch_mt<bf16_t, float, 0, false, false, NS>(x, ldx, B, K, N, wp, bias, rs, eps, outf, ldo_f, nullptr, 0, s, kgamma);
-    if (epi == 1) return skinny_launch_mt<bf16_t, float, 1, false, false, NS>(x, ldx, B, K, N, wp, bias, rs, eps, outf, ldo_f, nullptr, 0, s, kgamma);
-    if (epi == 2) return skinny_launch_mt<bf16_t, float, 2, false, false, NS>(x, ldx, B, K, N, wp, bias, rs, eps, outf, ldo_f, nullptr, 0, s, kgamma);
-    return MMX_EARG;
-}
+static_assert(skinny_select(MMX_BF16, MMX_BF16, XOP, 2, false)->launch == skinny_launch<bf16_t, bf16_t, 2, true, true, 1> &&
+              skinny_select(MMX_X3, MMX_F32, 0, 1, true)->launch == skinny_launch<bf16_t, float, 1, false, false, 3> &&
+              skinny_select(MMX_BF16, MMX_F32, 0, 1, true) && !skinny_select(MMX_BF16, MMX_F32, 0, 2, true) && !skinny_select(MMX_F32, MMX_F32, 0, 0, true) &&
+              !skinny_select(MMX_BF16, MMX_F32, XP, 0, false) && !skinny_select(MMX_F32, MMX_BF16, 0, 0, false) && !skinny_select(MMX_X3, MMX_F32, XP, 0, false));
+
 extern "C" int mmx_skinny_gemm(const void* x, int x_dtype, int64_t ldx, int B, int K, int N, const void* wp,
                                const float* bias, int rs, float eps, int epi, float* out_f32, int64_t ldo_f,
                                void* out_act, int64_t ldo_a, int dtype, int flags, const float* kgamma, hipStream_t stream) {
     MMX_CHECK_ARG(x && wp && B > 0 && B <= 64 && K > 0 && K % 32 == 0 && N > 0);
-    if (dtype == MMX_X2 || dtype == MMX_X3) {
-        // split build: fp32 row-major activations in, fp32 out (epi 1 writes SwiGLU(gate, up) to out_f32)
-        MMX_CHECK_ARG(x_dtype == MMX_F32 && flags == 0 && out_f32 && !out_act && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)wp % 16) == 0);
-        MMX_CHECK_ARG(!kgamma || ((uintptr_t)kgamma % 16) == 0);
-        return dtype == MMX_X2 ? skinny_launch_split<2>(epi, x, ldx, B, K, N, wp, bias, rs, eps, out_f32, ldo_f, stream, kgamma)
-                               : skinny_launch_split<3>(epi, x, ldx, B, K, N, wp, bias, rs, eps, out_f32, ldo_f, stream, kgamma);
+    const SkinnyForm* form = skinny_select(dtype, x_dtype, flags, epi, kgamma != nullptr);
+    MMX_CHECK_ARG(form);
+    MMX_CHECK_ARG(ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && (!kgamma || ((uintptr_t)kgamma % 16) == 0));
+    MMX_CHECK_ARG(!(flags & MMX_OUT_PACKED) || N % 32 == 0);
+    const bool split = dtype == MMX_X2 || dtype == MMX_X3;
+    // Kept as it was before the table, on purpose: the bf16 build's kgamma form checks neither the alignment of wp nor its output
+    // pointers (the engine's prompt chunks always pass both right); every other form does.
+    if (split || !kgamma) {
+        MMX_CHECK_ARG(((uintptr_t)wp % 16) == 0);
+        // split build: fp32 out only (epi 1 writes SwiGLU(gate, up) to out_f32); else epi 1 -> out_act, epi 2 -> out_f32, epi 0 -> either
+        if (split) MMX_CHECK_ARG(out_f32 && !out_act);
+        else MMX_CHECK_ARG(epi == 1 ? out_act != nullptr : (out_f32 != nullptr || (epi == 0 && out_act != nullptr)));
     }
-    if (kgamma) {
-        // bf16 build with the gain applied to fp32 activations in the kernel (weights packed WITHOUT kscale: the decode step
-        // of that build runs on csrc/decode.hip, whose producers apply the gain; this kernel serves its prompt chunks)
-        MMX_CHECK_ARG(dtype == MMX_BF16 && x_dtype == MMX_F32 && flags == 0 && ((uintptr_t)kgamma % 16) == 0 && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0);
-        if (epi == 0) return skinny_launch_mt<bf16_t, float, 0, false, false, 1>(x, ldx, B, K, N, wp, bias, rs, eps, out_f32, ldo_f, out_act, ldo_a, stream, kgamma);
-        if (epi == 1) return skinny_launch_mt<bf16_t, float, 1, false, false, 1>(x, ldx, B, K, N, wp, bias, rs, eps, out_f32, ldo_f, out_act, ldo_a, stream, kgamma);
-        return MMX_EARG;
-    }
-    MMX_CHECK_ARG((flags == 0 || flags == MMX_X_PACKED || flags == (MMX_X_PACKED | MMX_OUT_PACKED)) && (flags == 0 || x_dtype == dtype) &&
-                  (!(flags & MMX_OUT_PACKED) || N % 32 == 0));
-    MMX_CHECK_ARG(ldx % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)wp % 16) == 0);
-    MMX_CHECK_ARG(epi == 1 ? out_act != nullptr : (out_f32 != nullptr || (epi == 0 && out_act != nullptr)));
-    MMX_CHECK_ARG(epi != 2 || out_f32 != nullptr);
-    if (dtype == MMX_BF16) {
-        if (x_dtype == MMX_F32) return skinny_launch_layout<bf16_t, float>(flags, epi, x, ldx, B, K, N, wp, bias, rs, eps, out_f32, ldo_f, out_act, ldo_a, stream);
-        if (x_dtype == MMX_BF16) return skinny_launch_layout<bf16_t, bf16_t>(flags, epi, x, ldx, B, K, N, wp, bias, rs, eps, out_f32, ldo_f, out_act, ldo_a, stream);
-    } else if (dtype == MMX_F32 && x_dtype == MMX_F32) {
-        return skinny_launch_layout<float, float>(flags, epi, x, ldx, B, K, N, wp, bias, rs, eps, out_f32, ldo_f, out_act, ldo_a, stream);
-    }
-    return MMX_EARG;
+    return form->launch({x, ldx, B, K, N, wp, bias, rs, eps, out_f32, ldo_f, out_act, ldo_a, kgamma}, stream);
 }
 
 // ------------------------------------------------------------------------------------------ RoPE + paged KV append
@@ -426,12 +416,7 @@ __global__ void rope_kv_kernel(const float* __restrict__ qkv, long ldqkv, long q
         const int hh = i / HALF, d = i % HALF;
         const float x0 = src[hh * D + d], x1 = src[hh * D + d + HALF];
         float y0 = x0, y1 = x1;
-        if (hh < Hq + Hkv) {                            // q and k heads are rotated, v is not
-            const float ang = (float)p * inv_freq[d];
-            const float c = cosf(ang), s = sinf(ang);
-            y0 = x0 * c - x1 * s;
-            y1 = x1 * c + x0 * s;
-        }
+        if (hh < Hq + Hkv) rope_pair(nullptr, inv_freq, p, d, x0, x1, y0, y1);   // q and k heads are rotated, v is not
         if (hh < Hq) {
             T* o = q_out + (long)b * q_bs + (long)t * ldq + hh * D;
             o[d] = Cvt<T>::from_f(y0);
@@ -450,12 +435,12 @@ extern "C" int mmx_rope_kv_store(const float* qkv, int64_t ldqkv, int64_t qkv_bs
                                  int dtype, hipStream_t stream) {
     dtype = MMX_ACT_DTYPE(dtype);
     MMX_CHECK_ARG(qkv && inv_freq && pos && q_out && kc && vc && block_table && B > 0 && rows > 0 && D == 64 && page > 0);
-    dim3 grid(rows, B);
-    if (dtype == MMX_BF16) hipLaunchKernelGGL(rope_kv_kernel<bf16_t>, grid, dim3(256), 0, stream, qkv, ldqkv, qkv_bs, Hq, Hkv, inv_freq, pos, (bf16_t*)q_out, ldq, q_bs, (bf16_t*)kc, (bf16_t*)vc, block_table, max_pages, page);
-    else if (dtype == MMX_F32) hipLaunchKernelGGL(rope_kv_kernel<float>, grid, dim3(256), 0, stream, qkv, ldqkv, qkv_bs, Hq, Hkv, inv_freq, pos, (float*)q_out, ldq, q_bs, (float*)kc, (float*)vc, block_table, max_pages, page);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        using T = decltype(el);
+        hipLaunchKernelGGL(rope_kv_kernel<T>, dim3(rows, B), dim3(256), 0, stream, qkv, ldqkv, qkv_bs, Hq, Hkv, inv_freq, pos, (T*)q_out, ldq, q_bs,
+                           (T*)kc, (T*)vc, block_table, max_pages, page);
+        return launch_status();
+    });
 }
 
 // ------------------------------------------------------------------------------------------ paged causal GQA attention
@@ -521,15 +506,14 @@ extern "C" int mmx_paged_attn(const void* q, int64_t ldq, int64_t q_bs, int B, i
     const size_t max_ctx = (size_t)max_pages * page;
     size_t lds = (64 + 8 + 4 * 64 + max_ctx) * 4;
     MMX_CHECK_ARG(lds <= 160 * 1024);
-    dim3 grid(Hq, rows, B);
-    // the score row is sized by the block table (max_pages * page), not by the context: above 16056 positions it needs the opt-in
-    if (dtype == MMX_BF16) MMX_LDS_OPT_IN(paged_attn_kernel<bf16_t>, lds);
-    else if (dtype == MMX_F32) MMX_LDS_OPT_IN(paged_attn_kernel<float>, lds);
-    if (dtype == MMX_BF16) hipLaunchKernelGGL(paged_attn_kernel<bf16_t>, grid, dim3(256), lds, stream, (const bf16_t*)q, ldq, q_bs, Hq, Hkv, scale, pos, (const bf16_t*)kc, (const bf16_t*)vc, block_table, max_pages, page, (bf16_t*)out, ldo, o_bs);
-    else if (dtype == MMX_F32) hipLaunchKernelGGL(paged_attn_kernel<float>, grid, dim3(256), lds, stream, (const float*)q, ldq, q_bs, Hq, Hkv, scale, pos, (const float*)kc, (const float*)vc, block_table, max_pages, page, (float*)out, ldo, o_bs);
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    return dispatch_dtype(dtype, [&](auto el) {
+        using T = decltype(el);
+        // the score row is sized by the block table (max_pages * page), not by the context: above 16056 positions it needs the opt-in
+        MMX_LDS_OPT_IN(paged_attn_kernel<T>, lds);
+        hipLaunchKernelGGL(paged_attn_kernel<T>, dim3(Hq, rows, B), dim3(256), lds, stream, (const T*)q, ldq, q_bs, Hq, Hkv, scale, pos, (const T*)kc,
+                           (const T*)vc, block_table, max_pages, page, (T*)out, ldo, o_bs);
+        return launch_status();
+    });
 }
 
 // ------------------------------------------------------------------------------------------ fused decode attention
@@ -537,21 +521,6 @@ extern "C" int mmx_paged_attn(const void* q, int64_t ldq, int64_t q_bs, int B, i
 // Every (head, sequence) workgroup ropes the new key itself (so it does not wait for the cache write of the
 // one workgroup per kv head that appends it), reads the older keys/values from the paged cache with 16-byte
 // loads all in flight, and splits PV over 32 key groups x 8 channel chunks.
-template <typename T>
-__device__ __forceinline__ void load8(const T* p, float o[8]) {
-    if constexpr (sizeof(T) == 2) {
-        uint4 r = *reinterpret_cast<const uint4*>(p);
-        const unsigned w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            o[2 * i] = __uint_as_float(w[i] << 16);
-            o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    } else {
-        float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-    }
-}
 // 8 consecutive elements kept RAW in registers (16 B for bf16, 32 B for fp32): a thread holds the K and V chunks of
 // many keys in flight and only converts a chunk when it consumes it
 template <typename T>
@@ -584,6 +553,8 @@ struct Raw8 {
 // workgroups, each reading its K / V rows ONCE for two heads - at batch 32 and 7 heads per kv head 256 workgroups (one round of
 // the 256 CUs) instead of 448, and 4/7 of the L2 -> CU traffic that bounds this kernel (the cached rows are 205 KB per workgroup
 // at 400 fp32 keys: 2.9 us at the ~70 GB/s a CU draws from L2; every head's arithmetic is what it was, in the same order).
+// dynamic LDS of decode_attn_kernel<T, OM, HP>: the carve-up at the head of the kernel, in floats (+ the block-table row)
+constexpr size_t decode_attn_lds(int hp, int max_pages) { return ((size_t)hp * 64 + 2 * 64 + 2 * hp * 32 + (size_t)hp * 32 * 64 + (size_t)max_pages) * 4; }
 template <typename T, int OM, int HP>
 __global__ __launch_bounds__(256) void decode_attn_kernel(
     const float* __restrict__ qkv, long ldqkv, int Hq, int Hkv, const float* __restrict__ inv_freq,
@@ -627,16 +598,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     if (tid < (HP + 1) * HALF) {
         const int which = tid >> 5, d = tid & 31;      // 0 .. HP-1: q head h0 + which, HP: k head hk
         const float* x = src + (which < HP ? (h0 + min(which, nh - 1)) * D : (Hq + hk) * D);
-        float c, s;
-        if (rope_tab) {                                // [pos][cos 0..31 | sin 0..31], computed like HF on the host
-            c = rope_tab[(long)p * D + d];
-            s = rope_tab[(long)p * D + HALF + d];
-        } else {
-            const float ang = (float)p * inv_freq[d];
-            c = cosf(ang);
-            s = sinf(ang);
-        }
-        const float y0 = x[d] * c - x[d + HALF] * s, y1 = x[d + HALF] * c + x[d] * s;
+        float y0, y1;
+        rope_pair(rope_tab, inv_freq, p, d, x[d], x[d + HALF], y0, y1);
         if (which < HP) { qs[which * D + d] = y0 * sc2; qs[which * D + d + HALF] = y1 * sc2; }   // (a head beyond nh repeats the last one: never stored)
         else { kn[d] = Cvt<T>::to_f(Cvt<T>::from_f(y0)); kn[d + HALF] = Cvt<T>::to_f(Cvt<T>::from_f(y1)); }
     } else if (tid < (HP + 1) * HALF + D) {
@@ -731,27 +694,10 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
             L = __builtin_fmaf(glh[g2], w, L);
             o = __builtin_fmaf(ph[g2 * D + d], w, o);
         }
-        if constexpr (OM == 2) {
-            const int nkb = Hq * D / 32, col = h * D + d;
+        if constexpr (OM >= 2) {                       // split planes: 3 bf16 terms (OM 2) or 2 fp16 terms (OM 3) of o / L
+            const int nkb = Hq * D / 32;
             const long ps = (long)((nseq + 15) / 16) * nkb * 512;
-            const long idx = ((((long)(b >> 4) * nkb + (col >> 5)) * 64) + (((col & 31) >> 3) << 4) + (b & 15)) * 8 + (col & 7);
-            bf16_t* pl = reinterpret_cast<bf16_t*>(out);
-            const float v = o / L;
-            const bf16_t hh = f2bf(v);
-            const float r1 = v - bf2f(hh);
-            const bf16_t mm = f2bf(r1);
-            pl[idx] = hh;
-            pl[ps + idx] = mm;
-            pl[2 * ps + idx] = f2bf(r1 - bf2f(mm));
-        } else if constexpr (OM == 3) {
-            const int nkb = Hq * D / 32, col = h * D + d;
-            const long ps = (long)((nseq + 15) / 16) * nkb * 512;
-            const long idx = ((((long)(b >> 4) * nkb + (col >> 5)) * 64) + (((col & 31) >> 3) << 4) + (b & 15)) * 8 + (col & 7);
-            unsigned short* pl = reinterpret_cast<unsigned short*>(out);
-            const float v = o / L;
-            const _Float16 hh = (_Float16)v;
-            pl[idx] = __builtin_bit_cast(unsigned short, hh);
-            pl[ps + idx] = __builtin_bit_cast(unsigned short, (_Float16)(v - (float)hh));
+            store_split<OM == 2 ? 3 : 2, OM == 3>(reinterpret_cast<bf16_t*>(out), ps, act_index<8, long>(b, h * D + d, nkb), o / L);
         } else {
             out[OM == 1 ? act_packed_index<T>(b, h * D + d, Hq * D) : (long)b * ldo + h * D + d] = Cvt<T>::from_f(o / L);
         }
@@ -769,6 +715,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
 //   * P V on the VALU, shared across heads: lane (key sub-row, 8-channel chunk) loads 16 bytes of a V row once and
 //     feeds G accumulators; P reaches those lanes through a wave-private LDS patch [key][8 heads].
 //   * the 4 waves x 8 key sub-rows are merged once through LDS.
+// dynamic LDS of decode_attn_gqa_kernel<OPK, G>: qh, ql, kn, vn (bf16), then Pw, Aw, gm, gl, part (fp32) and the block-table row
+constexpr size_t decode_attn_gqa_lds(int G, int max_pages) { return (2 * 16 * 64 + 2 * 64) * 2 + (4 * 8 * 16 * 8 + 3 * 32 + (size_t)32 * G * 64 + (size_t)max_pages) * 4; }
 template <bool OPK, int G>
 __global__ __launch_bounds__(256) void decode_attn_gqa_kernel(
     const float* __restrict__ qkv, long ldqkv, int Hq, int Hkv, const float* __restrict__ inv_freq,
@@ -804,16 +752,8 @@ __global__ __launch_bounds__(256) void decode_attn_gqa_kernel(
         const int which = tid >> 5, d = tid & 31;
         if (which <= G) {
             const float* x = src + (which < G ? (hk * G + which) * D : (Hq + hk) * D);
-            float c, s;
-            if (rope_tab) {
-                c = rope_tab[(long)p * D + d];
-                s = rope_tab[(long)p * D + HALF + d];
-            } else {
-                const float ang = (float)p * inv_freq[d];
-                c = cosf(ang);
-                s = sinf(ang);
-            }
-            const float y0 = x[d] * c - x[d + HALF] * s, y1 = x[d + HALF] * c + x[d] * s;
+            float y0, y1;
+            rope_pair(rope_tab, inv_freq, p, d, x[d], x[d + HALF], y0, y1);
             if (which < G) {
                 const float a0 = y0 * sc2, a1 = y1 * sc2;
                 const bf16_t h0 = f2bf(a0), h1 = f2bf(a1);
@@ -981,43 +921,77 @@ __global__ __launch_bounds__(256) void decode_attn_gqa_kernel(
         out[OPK ? act_packed_index<bf16_t>(b, col, Hq * D) : (long)b * ldo + col] = f2bf(o / L);
     }
 }
+// Host side, as for the skinny GEMM: a launcher per kernel, a table with one row per instantiation - what a request is matched on,
+// its launcher, its workgroup count rule and its LDS bytes - and a constexpr selection from (dtype, MMX_DA_* bits, shape), none = MMX_EARG.
+struct DecodeAttnArgs {
+    const float* qkv; int64_t ldqkv; int B, Hq, Hkv; const float *inv_freq, *rope_tab; const int32_t *pos, *finished; void *kc, *vc;
+    const int32_t* block_table; int max_pages, page; float scale; void* out; int64_t ldo;
+};
+template <typename T, int OM, int HP>
+static int launch_da(const DecodeAttnArgs& a, unsigned wgs, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL((decode_attn_kernel<T, OM, HP>), dim3(wgs), dim3(256), lds, s, a.qkv, a.ldqkv, a.Hq, a.Hkv, a.inv_freq, a.rope_tab, a.pos, (T*)a.kc,
+                       (T*)a.vc, a.block_table, a.max_pages, a.page, a.scale, (T*)a.out, a.ldo, a.B, a.finished);
+    return launch_status();
+}
+template <bool OPK>
+static int launch_dg(const DecodeAttnArgs& a, unsigned wgs, size_t lds, hipStream_t s) {
+    MMX_CHECK_ARG(lds <= 160 * 1024);
+    MMX_LDS_OPT_IN((decode_attn_gqa_kernel<OPK, 7>), lds);
+    hipLaunchKernelGGL((decode_attn_gqa_kernel<OPK, 7>), dim3(wgs), dim3(256), lds, s, a.qkv, a.ldqkv, a.Hq, a.Hkv, a.inv_freq, a.rope_tab, a.pos,
+                       (bf16_t*)a.kc, (bf16_t*)a.vc, a.block_table, a.max_pages, a.scale, (bf16_t*)a.out, a.ldo, a.B, a.finished);
+    return launch_status();
+}
+struct DecodeAttnForm {
+    int dtype, om, hp;                                 // cache / output type, output mode (decode_attn_kernel's OM), heads per workgroup; hp 0: GQA-shared
+    int (*launch)(const DecodeAttnArgs&, unsigned, size_t, hipStream_t);
+    unsigned wgs(int B, int Hq, int Hkv) const {       // per head: (sequence, kv head) pairs padded to the 8 XCDs x sub-groups of hp heads
+        return hp ? 8 * ((Hkv * B + 7) / 8) * ((Hq / Hkv + hp - 1) / hp) : Hkv * B;
+    }
+    size_t lds(int max_pages) const { return hp ? decode_attn_lds(hp, max_pages) : decode_attn_gqa_lds(7, max_pages); }
+};
+template <typename T, int OM, int HP>
+constexpr DecodeAttnForm da() { return {sizeof(T) == 2 ? MMX_BF16 : MMX_F32, OM, HP, launch_da<T, OM, HP>}; }
+constexpr DecodeAttnForm DECODE_ATTN_FORMS[] = {
+    {MMX_BF16, 0, 0, launch_dg<false>}, {MMX_BF16, 1, 0, launch_dg<true>},
+    da<bf16_t, 0, 1>(), da<bf16_t, 0, 2>(), da<bf16_t, 1, 1>(), da<bf16_t, 1, 2>(),
+    da<float, 0, 1>(), da<float, 0, 2>(), da<float, 1, 1>(), da<float, 1, 2>(), da<float, 2, 1>(), da<float, 2, 2>(), da<float, 3, 1>(), da<float, 3, 2>(),
+};
+// dtype: after MMX_ACT_DTYPE.  bits: include/mmx_hip.h MMX_DA_*
+constexpr const DecodeAttnForm* decode_attn_select(int dtype, int bits, int page, int Hq, int Hkv, int B) {
+    if (bits < 0 || bits > 31) return nullptr;
+    const bool split = bits & MMX_DA_SPLIT, h2 = bits & MMX_DA_H2;
+    if ((split || h2) && (dtype != MMX_F32 || (bits & MMX_DA_PACKED) || (split && h2))) return nullptr;   // planes: fp32 kernel, one kind
+    const int om = h2 ? 3 : split ? 2 : bits & MMX_DA_PACKED;
+    // Two heads per workgroup only where one head per workgroup needs more than one round of the 256 CUs (batch > 18 at 14 heads: the
+    // kernel is bound by what a CU draws from L2 there - 882 against 916 us per decode step at batch 32); below that a workgroup's
+    // own latency chain is the bound and the second head only lengthens it
+    int hp = (bits & MMX_DA_ONE_HEAD) || (long)B * Hq <= 256 ? 1 : 2;
+    if (dtype == MMX_BF16 && page == 16 && Hq == 7 * Hkv && !(bits & MMX_DA_PER_HEAD)) hp = 0;            // GQA-shared
+    for (const DecodeAttnForm& f : DECODE_ATTN_FORMS)
+        if (f.dtype == dtype && f.om == om && f.hp == hp) return &f;
+    return nullptr;
+}
+// what the engines' decode steps launch (mmx/llm.py: LlmEngine._attn_kw; 14 query heads, 2 kv heads, 16-key pages), at the last batch
+// size with one head per workgroup and the first with two (B * Hq <= 256); and the library's own bf16 default, the GQA-shared kernel
+static_assert(decode_attn_select(MMX_BF16, MMX_DA_PACKED | MMX_DA_PER_HEAD, 16, 14, 2, 18)->launch == launch_da<bf16_t, 1, 1> && decode_attn_select(MMX_BF16, MMX_DA_PACKED | MMX_DA_PER_HEAD, 16, 14, 2, 19)->launch == launch_da<bf16_t, 1, 2>);
+static_assert(decode_attn_select(MMX_F32, MMX_DA_SPLIT | MMX_DA_PER_HEAD, 16, 14, 2, 18)->launch == launch_da<float, 2, 1> && decode_attn_select(MMX_F32, MMX_DA_SPLIT | MMX_DA_PER_HEAD, 16, 14, 2, 19)->launch == launch_da<float, 2, 2>);
+static_assert(decode_attn_select(MMX_F32, MMX_DA_H2 | MMX_DA_PER_HEAD, 16, 14, 2, 18)->launch == launch_da<float, 3, 1> && decode_attn_select(MMX_F32, MMX_DA_H2 | MMX_DA_PER_HEAD, 16, 14, 2, 19)->launch == launch_da<float, 3, 2>);
+static_assert(decode_attn_select(MMX_BF16, MMX_DA_PACKED, 16, 14, 2, 18)->launch == launch_dg<true> && decode_attn_select(MMX_BF16, MMX_DA_PACKED, 16, 14, 2, 19)->launch == launch_dg<true>);
+
 extern "C" int mmx_decode_attn_fin(const float* qkv, int64_t ldqkv, int B, int Hq, int Hkv, int D, const float* inv_freq,
                                    const float* rope_tab, const int32_t* pos, const int32_t* finished, void* kc, void* vc,
                                    const int32_t* block_table, int max_pages, int page, float scale, void* out, int64_t ldo, int dtype,
                                    int out_packed, hipStream_t stream) {
     dtype = MMX_ACT_DTYPE(dtype);
     MMX_CHECK_ARG(qkv && (inv_freq || rope_tab) && pos && kc && vc && block_table && out && B > 0 && D == 64 && Hq % Hkv == 0 && page > 0);
-    MMX_CHECK_ARG(out_packed >= 0 && out_packed <= 31);
-    const bool gqa_shared = !(out_packed & 2);         // bit 1: force the per-head kernel (A/B measurements, tests)
-    const bool split_out = out_packed & 4;             // bit 2: output as split planes (fp32 build of the kernel only)
-    const bool split_h2 = out_packed & 8;              // bit 3: output as two fp16 planes (MMX_H2; fp32 build of the kernel only)
-    // bit 4: one query head per workgroup whatever the batch (measurements, tests).  Default: two heads per workgroup only where one
-    // head per workgroup needs more than one round of the 256 CUs (batch > 18 at 14 heads: the kernel is bound by what a CU draws
-    // from L2 there - 882 against 916 us per decode step at batch 32); below that a workgroup's own latency chain is the bound and
-    // the second head only lengthens it
-    const bool one_head = (out_packed & 16) || (long)B * Hq <= 256;
-    MMX_CHECK_ARG(!(split_out || split_h2) || (dtype == MMX_F32 && !(out_packed & 1) && !(split_out && split_h2)));
-    out_packed &= 1;
-    const size_t max_ctx = (size_t)max_pages * page;
-    (void)max_ctx;
-    const int hp = one_head ? 1 : 2, nsub = (Hq / Hkv + hp - 1) / hp;
-    size_t lds = ((size_t)hp * 64 + 2 * 64 + 2 * hp * 32 + (size_t)hp * 32 * 64 + (size_t)max_pages) * 4;
-    MMX_CHECK_ARG(lds <= 64 * 1024);
-    dim3 grid(8 * ((Hkv * B + 7) / 8) * nsub);
-#define DA(T, OM) do { if (one_head) hipLaunchKernelGGL((decode_attn_kernel<T, OM, 1>), grid, dim3(256), lds, stream, qkv, ldqkv, Hq, Hkv, inv_freq, rope_tab, pos, (T*)kc, (T*)vc, block_table, max_pages, page, scale, (T*)out, ldo, B, finished); \
-                       else hipLaunchKernelGGL((decode_attn_kernel<T, OM, 2>), grid, dim3(256), lds, stream, qkv, ldqkv, Hq, Hkv, inv_freq, rope_tab, pos, (T*)kc, (T*)vc, block_table, max_pages, page, scale, (T*)out, ldo, B, finished); } while (0)
-    if (dtype == MMX_BF16 && page == 16 && Hq == 7 * Hkv && gqa_shared) {
-        const size_t lds2 = (2 * 16 * 64 + 2 * 64) * 2 + (4 * 8 * 16 * 8 + 3 * 32 + 32 * 7 * 64 + (size_t)max_pages) * 4;
-        MMX_CHECK_ARG(lds2 <= 160 * 1024);
-        if (out_packed) MMX_LDS_OPT_IN((decode_attn_gqa_kernel<true, 7>), lds2);
-        else MMX_LDS_OPT_IN((decode_attn_gqa_kernel<false, 7>), lds2);
-#define DG(OPK) hipLaunchKernelGGL((decode_attn_gqa_kernel<OPK, 7>), dim3(Hkv * B), dim3(256), lds2, stream, qkv, ldqkv, Hq, Hkv, inv_freq, rope_tab, pos, (bf16_t*)kc, (bf16_t*)vc, block_table, max_pages, scale, (bf16_t*)out, ldo, B, finished)
-        if (out_packed) DG(true); else DG(false);
-    } else if (dtype == MMX_BF16) { if (out_packed) DA(bf16_t, 1); else DA(bf16_t, 0); }
-    else if (dtype == MMX_F32) { if (split_h2) DA(float, 3); else if (split_out) DA(float, 2); else if (out_packed) DA(float, 1); else DA(float, 0); }
-    else return MMX_EARG;
-    MMX_LAUNCH_CHECK();
-    return MMX_OK;
+    const DecodeAttnForm* form = decode_attn_select(dtype, out_packed, page, Hq, Hkv, B);
+    MMX_CHECK_ARG(form);
+    // Kept as it was before the table: the per-head kernel's 64 KB bound on the block-table row holds for the GQA-shared forms too
+    // (at the heads per workgroup the batch would give the per-head kernel); it implies their own 160 KB bound
+    const bool one_head = (out_packed & MMX_DA_ONE_HEAD) || (long)B * Hq <= 256;
+    MMX_CHECK_ARG(decode_attn_lds(one_head ? 1 : 2, max_pages) <= 64 * 1024);
+    return form->launch({qkv, ldqkv, B, Hq, Hkv, inv_freq, rope_tab, pos, finished, kc, vc, block_table, max_pages, page, scale, out, ldo},
+                        form->wgs(B, Hq, Hkv), form->lds(max_pages), stream);
 }
 extern "C" int mmx_decode_attn(const float* qkv, int64_t ldqkv, int B, int Hq, int Hkv, int D, const float* inv_freq,
                                const float* rope_tab, const int32_t* pos, void* kc, void* vc, const int32_t* block_table, int max_pages,

@@ -225,6 +225,13 @@ class LlmEngine:
             raise ValueError(f"prompt_on={prompt_on!r}: {packs}" + ("" if gemm_packs else ", shared model without row-major copies,") + f" take {ok}")
         return decode, prompt_on or ("gemm" if planes_only else "gemm-batch" if B >= 4 and gemm_packs else "skinny")
 
+    @staticmethod
+    def _attn_kw(split, h2, B, gqa_min_batch):
+        """The decode attention form of the step on csrc/decode.hip (ops.decode_attn's switches; the static_asserts under
+        decode_attn_select in csrc/llm.hip pin the kernels they resolve to): its output is the o projection's operand - one
+        packed bf16 plane (bf16 build), three bf16 planes (split build) or two fp16 planes (h2)."""
+        return dict(per_head=bool(split or B < gqa_min_batch), out_split=("f16" if h2 else bool(split)), out_packed=not split)
+
     # ------------------------------------------------------------------ one transformer pass over `rows` tokens/seq
     def _layers(self, h, ha, B, rows, pos, block_table, packed=False):
         """The layers on mmx_skinny_gemm (prompt chunks; the decode step where decode_on is "skinny").
@@ -320,8 +327,8 @@ class LlmEngine:
                         tiles_per_wg=c["qkv"][0])
             # (bf16 build: one plane = the packed A-fragment order the attention kernels already write)
             ops.decode_attn(qkv, m.inv_freq, pos, m.kc[l], m.vc[l], block_table, S["xs_att"], B=B, Hq=m.Hq,
-                            Hkv=m.Hkv, page=m.page, dtype=m.dtype, rope_tab=m.rope_tab, per_head=(m.split or B < self.gqa_min_batch),
-                            out_split=("f16" if m.h2 else m.split), out_packed=not m.split, finished=fin)
+                            Hkv=m.Hkv, page=m.page, dtype=m.dtype, rope_tab=m.rope_tab, finished=fin,
+                            **self._attn_kw(m.split, m.h2, B, self.gqa_min_batch))
             ops.skinny2(S["xs_att"], w["wo"], B=B, K=m.Hq * m.D, N=H, dtype=dt, epi=2, out=h, xs_out=S["xs_b"],
                         gamma_next=w["g2"], ssq_out=S["ssq_b"], tiles_per_wg=c["o"][0])
             ops.skinny2(S["xs_b"], w["wgu"], B=B, K=H, N=I, dtype=dt, ssq_in=S["ssq_b"], eps=m.eps, epi=1, xs_out=S["xs_act"],

@@ -492,6 +492,12 @@ def paged_attn(q, pos, kc, vc, block_table, out, *, B, rows, Hq, Hkv, page, dtyp
                                 i64(ldo), i64(rows * ldo if o_bs is None else o_bs), dtype, stream()), "mmx_paged_attn")
 
 
+def decode_attn_bits(out_packed=False, per_head=False, out_split=False, one_head=False):
+    """decode_attn's switches as the MMX_DA_* bits of mmx_decode_attn's out_packed argument (include/mmx_hip.h)."""
+    return ((L.DA_PACKED if out_packed else 0) | (L.DA_PER_HEAD if per_head else 0) | (L.DA_ONE_HEAD if one_head else 0) |
+            (L.DA_H2 if out_split == "f16" else L.DA_SPLIT if out_split else 0))
+
+
 def decode_attn(qkv, inv_freq, pos, kc, vc, block_table, out, *, B, Hq, Hkv, page, dtype, rope_tab=None, out_packed=False,
                 per_head=False, out_split=False, one_head=False, ldqkv=None, ldo=None, finished=None):
     """per_head: the per-query-head kernel even where the GQA-shared one applies (measurements, tests); one_head: that kernel with
@@ -503,7 +509,7 @@ def decode_attn(qkv, inv_freq, pos, kc, vc, block_table, out, *, B, Hq, Hkv, pag
     assert finished is None or (finished.dtype == torch.int32 and finished.numel() >= B and finished.stride(-1) == 1)
     check(load().mmx_decode_attn_fin(_p(qkv), i64((Hq + 2 * Hkv) * 64 if ldqkv is None else ldqkv), B, Hq, Hkv, 64, _p(inv_freq), _p(rope_tab),
                                      _p(pos), _p(finished), _p(kc), _p(vc), _p(block_table), block_table.shape[1], page, C.c_float(0.125), _p(out),
-                                     i64(Hq * 64 if ldo is None else ldo), dtype, int(bool(out_packed)) | (2 if per_head else 0) | (8 if out_split == "f16" else (4 if out_split else 0)) | (16 if one_head else 0), stream()), "mmx_decode_attn_fin")
+                                     i64(Hq * 64 if ldo is None else ldo), dtype, decode_attn_bits(out_packed, per_head, out_split, one_head), stream()), "mmx_decode_attn_fin")
 
 
 def swiglu(gu, out, *, rows, I, dtype, ldgu=None, ldo=None):

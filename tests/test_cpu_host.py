@@ -341,3 +341,29 @@ def test_gated_fused_forms_are_the_pinned_defaults():
                 pinned.add(f"est_{fam}_kernel<{', '.join(a)}>")
     gated = [g for g in cr.GATED if g.startswith(("est_tail_kernel<", "est_resnet_kernel<"))]
     assert len(gated) == 17 and [g for g in gated if g not in pinned] == []
+
+
+def test_engine_decode_attention_forms_are_the_pinned_defaults():
+    """The decode attention kernel each build's decode step launches is pinned by the static_asserts under decode_attn_select in
+    csrc/llm.hip, at the last batch size with one query head per workgroup and the first with two (B * Hq <= 256).  What the engine
+    asks for (LlmEngine._dispatch -> the step on csrc/decode.hip, LlmEngine._attn_kw -> ops.decode_attn_bits) is one of the pinned
+    requests, and resolves to the output form the o projection of that build reads."""
+    from mmx import _lib, ops
+    from mmx.llm import LlmEngine
+    hdr = open(os.path.join(ROOT, "include", "mmx_hip.h")).read()
+    names = {n: int(v) for n, v in re.findall(r"#define (MMX_DA_\w+) (\d+)", hdr)}
+    assert names == {"MMX_DA_PACKED": _lib.DA_PACKED, "MMX_DA_PER_HEAD": _lib.DA_PER_HEAD, "MMX_DA_SPLIT": _lib.DA_SPLIT,
+                     "MMX_DA_H2": _lib.DA_H2, "MMX_DA_ONE_HEAD": _lib.DA_ONE_HEAD}
+    pinned = {}
+    for line in open(os.path.join(ROOT, "minimax-speech_amd", "csrc", "llm.hip")):
+        if line.startswith("static_assert(decode_attn_select("):
+            for dt, bits, B, launch in re.findall(r"decode_attn_select\((MMX_\w+), ([^,]+), 16, 14, 2, (\d+)\)->launch == (launch_d[ag]<[^>]*>)", line):
+                pinned[(dt, sum(names[b.strip()] for b in bits.split("|")), int(B))] = launch
+    assert len(pinned) == 8
+    # (dtype, h2) of the three builds -> the kernel's storage type and output mode OM (1 packed, 2 bf16 planes, 3 fp16 planes)
+    for (dtype, h2), (dt, T, om) in {(_lib.BF16, False): ("MMX_BF16", "bf16_t", 1), (_lib.X3, False): ("MMX_F32", "float", 2),
+                                     (_lib.X3, True): ("MMX_F32", "float", 3)}.items():
+        for B, hp in ((18, 1), (19, 2)):
+            assert LlmEngine._dispatch(dtype, h2, False, True, B, None, None, True)[0] == "planes"
+            bits = ops.decode_attn_bits(**LlmEngine._attn_kw(_lib.is_split(dtype), h2, B, LlmEngine.gqa_min_batch))
+            assert pinned[(dt, bits, B)] == f"launch_da<{T}, {om}, {hp}>"
