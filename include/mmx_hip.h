@@ -597,6 +597,46 @@ int mmx_resample_sinc(const float* wave, int64_t w_bs, int L, int B, const int32
                       int width, const float* taps, const int32_t* first, const int32_t* count, int cmax, float* out,
                       int64_t o_bs, int out_cols, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Loudness (csrc/loudness.hip; the definition is stated in mmx/loudness.py): ITU-R BS.1770-4 integrated loudness as
+ * dac-vae/audiotools/core/loudness.py computes it (Meter.integrated_loudness, LoudnessMixin.loudness) and the gain of
+ * core/effects.py:181-220 (normalize, ensure_max_of_audio), over a ragged batch, without a host sync.
+ *   rate: one with int(0.4 rate) == 4 * S, S = int(0.4 rate 0.25) (16 000, 22 050, 24 000, 44 100, 48 000 among them): a 400 ms block
+ *         is then four sub-blocks of S samples.  A row of len samples counts as n' = len + int((0.5 - len / rate) * rate) samples when it
+ *         is shorter than 0.5 s (zeros), and has nsub = ceil(n' / S) sub-blocks with MMX_LOUD_PAD (julius.core.unfold: the tail zero
+ *         padded), n' / S with MMX_LOUD_DROP (BS.1770 / pyloudnorm); its blocks are the nsub - 3 runs of four sub-blocks.
+ *   cap:  columns of the per-sub-block arrays, >= ceil(max(L, rate / 2 + 1) / S).
+ *   lens  int32 [rows] or NULL (= L), clamped to [0, L]; samples at or beyond lens[b] are never read.
+ *
+ * mmx_kweight_blocks: wave fp32 [B][w_bs >= L] mono rows ->
+ *   energy f64 [B][e_bs >= cap]: energy[b][i] = sum of squares of the K-weighted row over the samples of sub-block i below n' (the
+ *          tail block is padded AFTER the filter, as julius.core.unfold does), i < nsub; 0 from there to cap;
+ *   peak   fp32 [B]: max |x| over the row's len samples.
+ *   tab    f64 [10 + 16 * 8] in device memory (mmx/loudness.py tables): the two biquads (b0, b1, b2, a1, a2 each, a0 = 1; shelf first),
+ *          then row-major 4 x 4 powers of the transition matrix A of the cascade's transposed-direct-form-II state: A^(seg 2^k) for
+ *          k = 0 .. 6, then A^S.  seg: samples per lane, S % seg == 0, seg <= 64, S / seg <= 127.
+ *   work   f64 [B][cap][5]: scratch (sub-block states and peaks).
+ *   Three launches: zero-state segment walks and a scan over the lanes per sub-block; one wave per row carrying the state across
+ *   sub-blocks; the walk from the true state that sums the squares.  State and sums are fp64.  A row's values depend on its own
+ *   samples, length and rate only: solo and batched runs agree bit for bit.
+ * mmx_loudness_gate: one wave per clip of nch <= MMX_LOUD_MAX_CH adjacent rows (lens[clip * nch] is the clip's length) ->
+ *   lufs fp32 [nclips]: l_j = -0.691 + 10 log10 sum_c G[c] z[c][j], z = block energy / (0.4 rate); the blocks with l_j > -70 give
+ *   Gamma_r = (loudness of their mean z) - 10; the blocks above both give the result; no block, or a result below -70: -70.
+ *   G f64 [nch] in HOST memory or NULL (1, 1, 1, 1.41, 1.41).  want_gain: gain fp32 [nclips] = exp((target_db - lufs) ln10 / 20), or
+ *   max_peak / peak where that gain would lift the clip's peak above max_peak (then gain * peak <= max_peak in fp32).
+ *   mask uint8 [nclips][mask_bs >= cap - 3] or NULL: 1 for every block that passed both gates.
+ * mmx_scale_rows: out[b][j] = x[b][j] * gain[b / nch] for j < lens[b]; nothing else is written; out may be x. */
+#define MMX_LOUD_PAD 0
+#define MMX_LOUD_DROP 1
+#define MMX_LOUD_MAX_CH 5
+int mmx_kweight_blocks(const float* wave, int64_t w_bs, int L, int B, const int32_t* lens, int rate, int partial, const double* tab,
+                       int seg, double* work, int cap, double* energy, int64_t e_bs, float* peak, hipStream_t stream);
+int mmx_loudness_gate(const double* energy, int64_t e_bs, int cap, const float* peak, const int32_t* lens, int L, int nclips, int nch,
+                      const double* G, int rate, int partial, float* lufs, int want_gain, float target_db, float max_peak, float* gain,
+                      uint8_t* mask, int64_t mask_bs, hipStream_t stream);
+int mmx_scale_rows(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const float* gain, int nch, float* out,
+                   int64_t o_bs, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,11 +158,34 @@ class TtsEngine:
             ops.copy2d(l.contiguous(), F32, 0, 80, 1, zt[i], self.dtype, 0, 80, 1, rows=Ts[i], cols=80)
         return self.dac.decode_time_major(zt, len(lats), max(Ts), lens=(Ts if len(lats) > 1 else None))
 
+    def _level(self, wavs, loudness_db, rate=SAMPLE_RATE):
+        """Level matching of finished audio (mmx.loudness.normalize: BS.1770 integrated loudness brought to loudness_db LUFS, the
+        peak kept at or below 1.0; DACVAE.decompress's last step, dac-vae/base.py:285).  wavs: one waveform or a list, each of any
+        shape holding one mono clip; loudness_db: None (the input itself, nothing is launched), a float, or for a list one entry per
+        waveform (None entries stay as they are).  Every clip is metered alone, so its result does not depend on its companions;
+        the clips that share a target share one launch sequence.  No host sync."""
+        if loudness_db is None or (isinstance(loudness_db, (list, tuple)) and all(d is None for d in loudness_db)):
+            return wavs
+        from .loudness import normalize
+        if not isinstance(wavs, (list, tuple)):
+            return normalize([wavs.reshape(-1)], rate, float(loudness_db))[0][0].reshape(wavs.shape)
+        if isinstance(loudness_db, (list, tuple)) and len(loudness_db) != len(wavs):
+            raise ValueError("loudness_db: one value, or one entry per utterance")
+        dbs = [_own(loudness_db, b) for b in range(len(wavs))]
+        out = list(wavs)
+        for db in sorted({float(d) for d in dbs if d is not None}):
+            idx = [b for b, d in enumerate(dbs) if d is not None and float(d) == db]
+            for b, w in zip(idx, normalize([wavs[b].reshape(-1) for b in idx], rate, db)[0]):
+                out[b] = w.reshape(wavs[b].shape)
+        return out
+
     @torch.no_grad()
     def token2wav(self, token: torch.Tensor, prompt_token: torch.Tensor, prompt_feat: torch.Tensor,
-                  embedding: torch.Tensor, streaming=False, finalize=True) -> torch.Tensor:
-        """tokens [1,L] -> waveform [1, 1, 2*L*hop] (cli/model.py:285-319 with the vocoder swapped for DAC)."""
-        return self._latents2wav(self.flow.inference_time_major(token, prompt_token, prompt_feat, embedding, streaming, finalize))
+                  embedding: torch.Tensor, streaming=False, finalize=True, loudness_db=None) -> torch.Tensor:
+        """tokens [1,L] -> waveform [1, 1, 2*L*hop] (cli/model.py:285-319 with the vocoder swapped for DAC).
+        loudness_db: the waveform is brought to that integrated loudness (LUFS, peak <= 1.0; _level); None leaves it as decoded."""
+        wav = self._latents2wav(self.flow.inference_time_major(token, prompt_token, prompt_feat, embedding, streaming, finalize))
+        return self._level(wav, loudness_db)
 
     @torch.no_grad()
     def reference_embedding(self, reference_audio, sample_rate=24000, cache=None, resample=False) -> torch.Tensor:
@@ -237,25 +260,31 @@ class TtsEngine:
         return out
 
     @torch.no_grad()
-    def prompt_from_clip(self, wave, sample_rate, prompt_text=None, noise=None, generator=None, via_16k=True) -> dict:
+    def prompt_from_clip(self, wave, sample_rate, prompt_text=None, noise=None, generator=None, via_16k=True, normalize_db=None) -> dict:
         """prompt_from_audio from ONE recording (mono [n] / [1, n]) at any rate: the two resamplings happen here, on the device
         (mmx.resample.Resample).  via_16k=True is the reference's inference route: the file is brought to 16 kHz
         (utils/file_utils.py:44-50 load_wav) and the features are taken from THAT clip brought to 24 kHz (cli/frontend.py:157-162);
         via_16k=False brings the source to each rate directly, as the dataset tools do (tools/extract_speech_token.py:30,
-        tools/extract_embedding.py:30).  A rate that is already the wanted one is not resampled."""
+        tools/extract_embedding.py:30).  A rate that is already the wanted one is not resampled.
+        normalize_db: the clip is first brought to that integrated loudness at its own rate (LUFS, peak <= 1.0; _level, as
+        DACVAE.compress normalises to -16 before it encodes, dac-vae/base.py:166-180), so tokens, latents and embedding all see the
+        same level-matched clip; None takes the clip at the level it has."""
         from .resample import Resample
-        w = wave.to(self.dev, torch.float32).reshape(-1)
+        w = self._level(wave.to(self.dev, torch.float32).reshape(-1), normalize_db, int(sample_rate))
         w16 = Resample(sample_rate, 16000)(w)
         w24 = Resample(16000, SAMPLE_RATE)(w16) if via_16k else Resample(sample_rate, SAMPLE_RATE)(w)
         return self.prompt_from_audio(w16, w24, prompt_text, noise, generator)
 
     @torch.no_grad()
-    def prompts_from_clips(self, waves, sample_rates, prompt_texts=None, noises=None, generator=None, via_16k=True) -> List[dict]:
+    def prompts_from_clips(self, waves, sample_rates, prompt_texts=None, noises=None, generator=None, via_16k=True,
+                           normalize_db=None) -> List[dict]:
         """prompt_from_clip for a list of recordings (mono [n] / [1, n]; sample_rates: one rate or one per clip) with the batched
         stages run once: the clips that share a rate go through ONE resample launch per target rate (mmx.resample.resample),
         all of them through ONE speech-tokenizer batch and ONE DAC-VAE encode (DacEncoderEngine.encode_ragged); the speaker
         embedding stays one reference_embedding per clip.  Entry i is the dict prompt_from_clip(waves[i], ...) returns, bit for
-        bit where noises[i] [80, frames] is given (a `generator` instead gives one draw for the batch, each clip its own rows)."""
+        bit where noises[i] [80, frames] is given (a `generator` instead gives one draw for the batch, each clip its own rows).
+        normalize_db (one value, or one per clip with None entries): as prompt_from_clip, each clip metered alone at its own rate,
+        the clips that share a rate and a target in one launch sequence."""
         from .resample import resample as resample_clips
         n = len(waves)
         rates = [int(sample_rates)] * n if isinstance(sample_rates, (int, float)) else [int(r) for r in sample_rates]
@@ -264,6 +293,13 @@ class TtsEngine:
         if n == 0:
             return []
         ws = [w.to(self.dev, torch.float32).reshape(-1) for w in waves]
+        if isinstance(normalize_db, (list, tuple)) and len(normalize_db) != n:
+            raise ValueError("prompts_from_clips: normalize_db is one value or per clip")
+        if normalize_db is not None:
+            for r in sorted(set(rates)):
+                idx = [i for i in range(n) if rates[i] == r]
+                for i, w in zip(idx, self._level([ws[i] for i in idx], [_own(normalize_db, i) for i in idx], r)):
+                    ws[i] = w
 
         def by_rate(clips, src_rates, new):
             out = [None] * n
@@ -292,20 +328,20 @@ class TtsEngine:
 
     @torch.no_grad()
     def voice_conversion(self, source_wave, source_rate, flow_prompt_speech_token, prompt_speech_feat, flow_embedding, speed=1.0,
-                         prompt_text=None, llm_prompt_speech_token=None) -> torch.Tensor:
+                         prompt_text=None, llm_prompt_speech_token=None, loudness_db=None) -> torch.Tensor:
         """The words of `source_wave` (mono [n] / [1, n] at `source_rate`) in the prompt's voice, non-streaming: frontend_vc
         (cli/frontend.py:205-213) and CosyVoice2.inference_vc (cli/cosyvoice.py:132-139 -> cli/model.py:331-335, the source's speech
         tokens take the place of the LM's).  Source -> 16 kHz -> the S3 tokenizer -> token2wav with the prompt -> [1, 1, 2 * tokens *
         hop].  Takes the splat of a prompt_from_clip / prompt_from_audio dict: eng.voice_conversion(src, rate, **prompt); the LM's
         keys (prompt_text, llm_prompt_speech_token) are not used.  speed != 1: the latent frames are resampled linearly in time
-        to int(frames / speed) before the decoder (cli/model.py:312-315)."""
+        to int(frames / speed) before the decoder (cli/model.py:312-315).  loudness_db: as token2wav."""
         from .resample import Resample
         w16 = Resample(source_rate, 16000)(source_wave.to(self.dev, torch.float32).reshape(-1))
         tok = self.s3tok.tokenize([w16])[0].to(torch.long).reshape(1, -1)
         if speed == 1.0:
-            return self.token2wav(tok, flow_prompt_speech_token, prompt_speech_feat, flow_embedding)
+            return self.token2wav(tok, flow_prompt_speech_token, prompt_speech_feat, flow_embedding, loudness_db=loudness_db)
         lat = self.flow.inference_time_major(tok, flow_prompt_speech_token, prompt_speech_feat, flow_embedding, False, True)
-        return self._latents2wav(ops.resample_linear(lat.float().t(), int(lat.shape[0] / speed)).t().contiguous())
+        return self._level(self._latents2wav(ops.resample_linear(lat.float().t(), int(lat.shape[0] / speed)).t().contiguous()), loudness_db)
 
     def _embedding_arg(self, flow_embedding, reference_audio, sample_rate):
         if (flow_embedding is None) == (reference_audio is None):
@@ -314,13 +350,13 @@ class TtsEngine:
 
     @torch.no_grad()
     def tts(self, text, flow_embedding=None, prompt_text=None, llm_prompt_speech_token=None, flow_prompt_speech_token=None,
-            prompt_speech_feat=None, seed=0, exact_steps=None, reference_audio=None, sample_rate=24000) -> torch.Tensor:
+            prompt_speech_feat=None, seed=0, exact_steps=None, reference_audio=None, sample_rate=24000, loudness_db=None) -> torch.Tensor:
         """One utterance, non-streaming (cli/model.py:321-386 `stream=False` branch).  reference_audio (instead of
-        flow_embedding): the voice as a recording, see reference_embedding."""
+        flow_embedding): the voice as a recording, see reference_embedding.  loudness_db: as token2wav."""
         flow_embedding = self._embedding_arg(flow_embedding, reference_audio, sample_rate)
         toks = self.generate_tokens([text], [prompt_text], [llm_prompt_speech_token], seed=seed, exact_steps=exact_steps)[0]
         return self.token2wav(toks.reshape(1, -1), self._prompt(flow_prompt_speech_token), self._prompt(prompt_speech_feat, feat=True),
-                              flow_embedding)
+                              flow_embedding, loudness_db=loudness_db)
 
     MEL_CACHE = 8            # cli/model.py:258: frames of overlap between two passes
 
@@ -356,7 +392,9 @@ class TtsEngine:
         rendered from; `forced` [1, steps] teacher-forces the accepted ids (LlmEngine.start).  cache=True: hops solve only
         their new frames (FlowEngine.StreamState); cache=False recomputes all frames at every hop, as the reference does.
         reference_audio (instead of flow_embedding): the voice as a recording (reference_embedding), embedded once before the
-        first hop."""
+        first hop.
+        There is no loudness_db here: integrated loudness (mmx.loudness) is a property of the whole utterance, which a stream has
+        not seen when it emits its first chunk.  Level-match the prompt (prompt_from_clip(normalize_db=...)) or the joined chunks."""
         assert self.llm.B == 1
         flow_embedding = self._embedding_arg(flow_embedding, reference_audio, sample_rate)
         fpt, pf = self._prompt(flow_prompt_speech_token), self._prompt(prompt_speech_feat, feat=True)
@@ -532,7 +570,8 @@ class TtsEngine:
     def tts_batch(self, texts, flow_embeddings=None, seed=0, exact_steps=None, group_size=8, max_pad_ratio=2.0,
                   frame_quantum=32, overlap=True, poll_every=8, flow_workers=2, hold_steps=60, tail_active=0, polite=True,
                   prompt_texts=None, llm_prompt_speech_tokens=None, flow_prompt_speech_tokens=None,
-                  prompt_speech_feats=None, samplers=None, seeds=None, reference_audio=None, sample_rate=24000) -> List[torch.Tensor]:
+                  prompt_speech_feats=None, samplers=None, seeds=None, reference_audio=None, sample_rate=24000,
+                  loudness_db=None) -> List[torch.Tensor]:
         """Throughput path for a batch of independent utterances (BASELINE config 4, one rank's share): one batched
         AR decode for all of them; as sequences finish (shortest first) their flow + DAC work — per-utterance
         conformer encoder, ODE solves batched over groups of similar length (zero padded + masked), DAC decode — is
@@ -558,7 +597,10 @@ class TtsEngine:
         more of the chip left to the decode loop's launches); the groups of the final poll use the fastest tiling.
         tail_active > 0: once at most that many sequences are still decoding, a finished utterance no longer waits for
         companions when a flow worker is (predicted) idle - the decode loop is the critical path, and whatever the last
-        utterances still have to do after their last token is what the step ends on."""
+        utterances still have to do after their last token is what the step ends on.
+        loudness_db (one value, or one per utterance with None entries): every utterance is brought to that integrated loudness
+        (LUFS, peak <= 1.0; _level) once all are decoded, each metered alone: the result does not depend on groups or schedule, and
+        equals mmx.loudness.normalize of the loudness_db=None result.  None: nothing is measured or launched."""
         B = len(texts)
         if reference_audio is None and flow_embeddings is None:
             raise ValueError("give flow_embeddings or reference_audio")
@@ -587,7 +629,7 @@ class TtsEngine:
             order = sorted(range(B), key=lambda b: (n[b], b))
             for grp in groups(order, [2 * (v + plen[b]) for b, v in enumerate(n)], group_size, max_pad_ratio, frame_quantum):
                 self._flow_dac_group(grp, toks, flow_embeddings, wavs, frame_quantum, prompts=prompts)
-            return wavs
+            return self._level(wavs, loudness_db)
 
         # ---- start: flow workers, scheduler, decode loop
         if not hasattr(self, "_sides") or len(self._sides) != flow_workers:
@@ -686,7 +728,7 @@ class TtsEngine:
         self.last_host = dict(decode_steps=done, lm_issue_ms=round(issue_s * 1e3, 2), lm_done_ms=round((t_lm - t0) * 1e3, 1),
                               call_ms=round((time.perf_counter() - t0) * 1e3, 1))
         self._refit_sched(done, (t_lm - t0) * 1e3, group_events, steady=(Graphed.cold_calls == cold0 and B == NS))
-        return wavs
+        return self._level(wavs, loudness_db)
 
     def _poll_finished(self, call, step, final):
         """A poll of tts_batch's decode loop (`call`: that call's state), step 1: reads the finished flags once; the utterances that
