@@ -49,7 +49,13 @@ typedef struct ihipStream_t* hipStream_t;
 #define MMX_X3W 0x13
 /* fp16 planes of the LM decode step (mmx_skinny2, mmx_decode_prep, mmx_decode_attn's split output only): activations as TWO fp16
  * planes hi + lo (22 significant bits), weights fp16 and stored * 2^8 - one plane for a bf16-representable checkpoint (MMX_H2),
- * two planes hi + lo for an fp32 checkpoint (MMX_H2W); v_mfma_f32_16x16x32_f16.  |activation| < 65504, |weight| < 255. */
+ * two planes hi + lo for an fp32 checkpoint (MMX_H2W); v_mfma_f32_16x16x32_f16.  Range: |weight| < 255, and for an activation
+ * v (= x * gain of its consumer)
+ *   |v| < 65520: at or past it the planes are inf / -inf, the products NaN, and mmx_sample_step* ends the sequence with error 3;
+ *   the planes hold v to max(2^-22 |v|, 2^-25): 22 bits only where |v| is well above 2^-3.  Per row of a projection (max |err| over
+ *   the row / max |ref| of the row, against float64 on exact operands) that is < 3e-6 for rows of scale >= 2^-6 and grows as
+ *   2^-25 / scale below: 3.5e-5 at 2^-10, 3.2e-4 at 2^-14, 2.6e-2 at 2^-20 (measured on MI355X = the format's own figures: the MFMA
+ *   keeps subnormal fp16 operands).  Nothing fails at the lower end; MMX_X3 has no such edge. */
 #define MMX_H2 4
 #define MMX_H2W 0x14
 
@@ -365,7 +371,11 @@ int mmx_swiglu(const float* gu, int64_t ldgu, int rows, int I, void* out, int64_
  * forced != NULL: teacher forcing, forced[b*max_out + step] replaces the accepted token (the sampled id is
  * still recorded in sampled[b][step]).  logp_out (optional) receives log_softmax(logits).
  * error (field 7): 0 none; 1 = 100 EOS re-draws under ignore_eos still gave EOS (llm.py:271-273 raises there; the id is accepted);
- *   2 = the sequence's column of the sampler table is out of range (mmx_sample_step_tab only, see below). */
+ *   2 = the sequence's column of the sampler table is out of range (mmx_sample_step_tab only, see below);
+ *   3 = the sequence's logits are not finite - a NaN, a +inf, or every one of them -inf, which is what an activation past the
+ *       range of the fp16 planes (MMX_H2 above) turns into: state.finished = 1 for THAT sequence, nothing is drawn, its pos /
+ *       step / n_out, out_tokens, sampled and next_x rows keep what they held (logp_out of the row is unspecified); the other
+ *       sequences of the launch are not affected.  -inf among finite logits is legal (probability 0) and not flagged. */
 int mmx_sample_step(const float* logits, int64_t ldl, int V, int B, int eos_id, int top_k, float top_p,
                     int win_size, float tau_r, uint64_t seed, int32_t* state, int32_t* out_tokens, int max_out,
                     int32_t* sampled, const int32_t* forced, const float* speech_emb, int E, float* next_x,

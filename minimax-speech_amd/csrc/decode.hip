@@ -28,7 +28,14 @@
 // A bf16-representable checkpoint converts to fp16 exactly (its weights are scaled by 2^8 at load so that the small ones stay
 // normal numbers; the epilogue multiplies by 2^-8) and costs two MFMAs per fragment on two thirds of the activation bytes of the
 // three-bf16-plane form; an fp32 checkpoint is two fp16 planes (MMX_H2W: 4 bytes per weight, three MFMAs per fragment) instead
-// of three bf16 planes (MMX_X3W: 6 bytes, six MFMAs).  Range: |activation| < 65504, |weight| < 255.
+// of three bf16 planes (MMX_X3W: 6 bytes, six MFMAs).
+// Range (tests/test_lm_planes_host.py, tests/test_gpu_lm_planes.py), |weight| < 255 and two ends for x * gamma:
+//   upper: |x * gamma| < 65520.  At or past it hi = inf and lo = -inf, the MFMA yields NaN, every logit of the sequence is NaN and
+//          the sampler ends the sequence with error 3 (csrc/sampler.hip) - loud, never a wrong id.
+//   lower: the planes hold v to max(2^-22 |v|, 2^-25).  A projection's per-row error (max |err| / max |ref| of the row, float64 on
+//          exact operands) is below 3e-6 for rows of scale 2^-6 and above, then grows as 2^-25 / scale: measured on MI355X
+//          1.5e-6 at 2^-6, 3.5e-5 at 2^-10, 3.2e-4 at 2^-14, 2.6e-2 at 2^-20 (1.6e-7 .. 2.8e-7 from 2^-3 to 2^12) - exactly the
+//          format's own figures: v_mfma_f32_16x16x32_f16 keeps subnormal fp16 operands (flushed, 2^-3 would show 2.7e-4).
 #include "act_layout.h"
 
 namespace {

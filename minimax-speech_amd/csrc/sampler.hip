@@ -104,7 +104,7 @@ struct SampParams {
 };
 struct SampState { int pos, step, n_out, finished, min_len, max_len, seq; };     // fields 0..6 of `state`, read by the entry kernel
 constexpr int SAMP_RAS = 0, SAMP_NUCLEUS = 1, SAMP_RANDOM = 2;
-constexpr int SAMP_ERR_TRIALS = 1, SAMP_ERR_PARAMS = 2;     // state field 7
+constexpr int SAMP_ERR_TRIALS = 1, SAMP_ERR_PARAMS = 2, SAMP_ERR_NONFINITE = 3;     // state field 7
 
 // MODES = false: the scalar entry point (RAS only, parameters checked on the host); true: the table entry point (the column's
 // mode and ranges are checked here, per sequence)
@@ -159,6 +159,14 @@ __device__ __forceinline__ void sample_step_body(
     for (int i = 0; i < SAMP_MAXV; ++i) se += (tid + i * SAMP_THREADS < V) ? expf(x[i] - mx) : 0.f;
     se = block_sum(se, shf);
     const float lse = logf(se);
+    // finite logits (a few -inf among them included) give 1 <= se <= V; a NaN, a +inf or a row of -inf makes se - and lse - NaN
+    // (+inf - +inf and -inf - -inf are NaN), and the ranking below would compare NaNs: no threshold, no candidate, an arbitrary id.
+    // Such a row (an overflowed fp16 plane upstream, include/mmx_hip.h MMX_H2) ends its own sequence instead, as a bad table
+    // column does: nothing is drawn or written.  lse is the same value in every thread of the block.
+    if (!(fabsf(lse) < INFINITY)) {
+        if (tid == 0) { ST(7) = SAMP_ERR_NONFINITE; ST(3) = 1; }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < SAMP_MAXV; ++i) {
         int idx = tid + i * SAMP_THREADS;

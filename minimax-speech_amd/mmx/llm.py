@@ -664,9 +664,24 @@ class LlmEngine:
             self._decode = Graphed(self._decode_step, self.use_graphs)
         self._graph_key = key
 
+    def raise_nonfinite(self, err):
+        """err: state[ST_ERR] of the slots a caller has just read back.  Code 3 (include/mmx_hip.h): the sampler met logits that are
+        not finite and ended the sequence without drawing - an activation left the range of the fp16 planes."""
+        bad = [s_ for s_, e in enumerate(err) if e == 3]
+        if bad:
+            raise RuntimeError(f"slot {bad[0]}: non-finite logits (fp16 plane range: lm_planes='bf16x3')" +
+                               (f"; also slots {bad[1:]}" if len(bad) > 1 else ""))
+
+    def host_state(self) -> List[List[int]]:
+        """The loop state as host lists [field][slot] in ONE device-to-host copy (the poll of a decode loop: finished flags,
+        counts and error codes together); raises for a slot whose logits were not finite."""
+        st = self.state.tolist()
+        self.raise_nonfinite(st[ST_ERR])
+        return st
+
     def run(self, max_steps: int, poll_every: int = 8) -> List[List[int]]:
         """Decode until every sequence finished or max_steps tokens were tried; returns accepted tokens per sequence."""
-        done = 1                                          # start() already sampled step 0
+        done, st = 1, None                                # start() already sampled step 0
         while done < max_steps:
             n = min(poll_every, max_steps - done)
             if self.reserve_ahead < (1 << 30):
@@ -674,9 +689,12 @@ class LlmEngine:
             for _ in range(n):
                 self._decode()
             done += n
-            if bool(self.state[ST_FIN].all().item()):
+            st = self.host_state()
+            if all(st[ST_FIN]):
                 break
-        return self.tokens()
+        if st is None:                                    # max_steps <= 1: start()'s own draw is the only one to check
+            st = self.host_state()
+        return self.tokens(st[ST_NOUT])
 
     @torch.no_grad()
     def run_queue(self, requests, seed=0, poll_every: int = 8, ahead: int = 32):
@@ -696,8 +714,8 @@ class LlmEngine:
         owner = [-1] * self.B
         nxt = 0
         while True:
-            fin = self.state[ST_FIN].tolist()
-            nout = self.state[ST_NOUT].tolist()
+            st = self.host_state()
+            fin, nout = st[ST_FIN], st[ST_NOUT]
             for s_ in range(self.B):
                 if owner[s_] >= 0 and fin[s_]:
                     out[owner[s_]] = self.out_tokens[s_, :nout[s_]].tolist()
@@ -767,6 +785,7 @@ class LlmEngine:
         err = int(self.state[ST_ERR, 0].item())
         if err == 2:
             raise RuntimeError("the sampler table's column is out of range (include/mmx_hip.h, mmx_sample_step_tab)")
+        self.raise_nonfinite([err])
         if err:
             raise RuntimeError("sampling reaches max_trials 100 and still get eos when ignore_eos is True, check your input!")
         s["rows"] += n
@@ -794,7 +813,8 @@ class LlmEngine:
         n = self.state[ST_NOUT].tolist() if n is None else n
         return [self.out_tokens[s_, :n[s_]].to(torch.int64) for s_ in (range(self.B) if slots is None else slots)]
 
-    def tokens(self) -> List[List[int]]:
-        n = self.state[ST_NOUT].tolist()
+    def tokens(self, n=None) -> List[List[int]]:
+        """n: state[ST_NOUT] as a host list, for a caller that has read it already."""
+        n = self.state[ST_NOUT].tolist() if n is None else n
         t = self.out_tokens.cpu()
         return [t[b, :n[b]].tolist() for b in range(self.B)]

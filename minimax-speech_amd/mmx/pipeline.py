@@ -18,7 +18,7 @@ from . import ops
 from ._lib import BF16, F32, TORCH_DT, X2, X3, is_split
 from .dac import DacDecoderEngine
 from .flow import FlowEngine, Graphed
-from .llm import ST_FIN, ST_NOUT, ST_POS, LlmEngine
+from .llm import ST_ERR, ST_FIN, ST_NOUT, ST_POS, LlmEngine
 from .sched import GroupScheduler, groups
 
 TOKEN_RATE = 25          # FSQ tokens per second (config.yaml:12)
@@ -462,6 +462,7 @@ class TtsEngine:
             while True:
                 with torch.cuda.stream(lm):
                     st = self.llm.state[:, 0].tolist()         # D2H copy on the LM stream: waits for the steps issued so far
+                self.llm.raise_nonfinite([st[ST_ERR]])
                 n_out, finished = st[ST_NOUT], bool(st[ST_FIN]) or done >= mx
                 this_hop = token_hop + pad if offset == 0 else token_hop          # model.py:341
                 while n_out - offset >= this_hop + L:
@@ -734,8 +735,8 @@ class TtsEngine:
         """A poll of tts_batch's decode loop (`call`: that call's state), step 1: reads the finished flags once; the utterances that
         finished since the last poll (at the final one: all that are left) arrive at the scheduler, shortest first.  Returns the flags."""
         eng, slots = call.eng, call.slots
-        fin = eng.state[ST_FIN].tolist()
-        n = eng.state[ST_NOUT].tolist()
+        st = eng.host_state()                             # (raises for a slot whose logits were not finite)
+        fin, n = st[ST_FIN], st[ST_NOUT]
         new = sorted([s_ for s_ in range(len(slots)) if (fin[s_] or final) and slots[s_] not in call.harvested],
                      key=lambda s_: (n[s_], slots[s_]))
         for s_, ids in zip(new, eng.accepted(new, n)):

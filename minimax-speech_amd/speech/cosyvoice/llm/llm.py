@@ -351,7 +351,7 @@ class Qwen2LM(EngineHost):
             lm_input = None
 
     def _decode_loop(self, eng, x, min_len, max_len, sampling=25):
-        from mmx.llm import ST_FIN, ST_NOUT
+        from mmx.llm import ST_ERR, ST_FIN, ST_NOUT
         spec = self._sampler_spec()
         if spec is None:
             yield from self._decode_loop_host(eng, x, min_len, max_len, sampling)
@@ -361,6 +361,7 @@ class Qwen2LM(EngineHost):
         done = 1
         while True:
             st = eng.state[:, 0].tolist()
+            eng.raise_nonfinite([st[ST_ERR]])
             toks = eng.out_tokens[0, sent:st[ST_NOUT]].tolist()
             for t in toks:
                 yield t
