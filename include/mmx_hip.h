@@ -647,6 +647,48 @@ int mmx_loudness_gate(const double* energy, int64_t e_bs, int cap, const float* 
 int mmx_scale_rows(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const float* gain, int nch, float* out,
                    int64_t o_bs, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Audio distances (csrc/metrics.hip; the definitions are stated in mmx/metrics.py): what the reference's DAC-VAE validation step
+ * reports (dac-vae/train.py:706-709 through dac-vae/loss.py MultiScaleSTFTLoss, MelSpectrogramLoss, L1Loss, SISDRLoss) and what its
+ * latent extractor writes per decoded sample (extract_dac_latents.py:89-95), between an estimate x and a reference y: two ragged
+ * batches of mono rows of equal per-clip length, without a host sync.
+ *   x, y  fp32 [B][x_bs / y_bs >= L];  lens int32 [B] or NULL (= L): valid samples per clip, the same for x and y; samples at or
+ *         beyond lens[b] are never read.
+ *
+ * mmx_spec_dist: ONE scale of the spectral distance, the arithmetic of AudioSignal.stft / mel_spectrogram
+ * (audiotools/core/audio_signal.py:1185-1212, 1354-1369): torch.stft(center=True) - reflection by n_fft / 2 on each side, done as
+ * index arithmetic on the row - with a periodic Hann window of n_fft samples, hop = n_fft / 4, frames(len) = 1 + len / hop frames,
+ * magnitude sqrt(re^2 + im^2) of all n_fft / 2 + 1 bins, and with n_mels > 0 the mel projection of the magnitudes.
+ *   h_lens: the values of lens in HOST memory (given exactly when lens is), so that the call can refuse a clip before a launch.
+ *   basis bf16 [3][2 * nbp][n_fft], nbp = n_fft / 2 + 1 rounded up to 32: three planes hi + mid + lo of the float64 values
+ *         hann[k] * cos(2 pi i k / n_fft) (row 32 * (i / 16) + i % 16) and hann[k] * sin(..) (that row + 16), rows of bins
+ *         > n_fft / 2 zero, each plane in mmx_pack_skinny order (mmx_logmel's layout with bin0 = 0 and every bin);
+ *   filt  bf16 [3][mp][nbp], mp = n_mels rounded up to 16: three planes of the fp32 filterbank [n_mels][n_fft / 2 + 1] (zero
+ *         padded), each plane in mmx_pack_skinny order; NULL exactly when n_mels == 0 (STFT mode: the bins themselves).
+ *   Both products run on the bf16 MFMA with samples and magnitudes split into three bf16 terms and every term pair s + p < 3
+ *   kept, fp32 accumulation (mmx_logmel's arithmetic).  With a, b the values of x and y at one (frame, column), column = bin or mel:
+ *   out   f64 [B][2]:  out[b][0] = mean |log10(max(a, eps)^pow) - log10(max(b, eps)^pow)|,   out[b][1] = mean |a - b|,
+ *         both over the clip's own frames(lens[b]) frames x the true n_fft / 2 + 1 bins (or n_mels mels).  Every term from the
+ *         subtraction on is fp64 and summed in a fixed order: per 16-frame tile into work, then per clip by the finishing launch.
+ *   work  f64 [B][cap][2], cap >= ceil(frames(L) / 16): scratch.
+ *   A workgroup takes 16 frames of one clip through both signals; no spectrogram is written.  A clip's two numbers depend on its
+ *   own samples and length alone: solo and batched runs agree bit for bit, and x == y gives exactly 0.
+ * MMX_EARG, before anything is launched: n_fft < 32 or not a multiple of 32; a clip (or L) with at most n_fft / 2 samples (the
+ *   reflection is undefined; torch raises there too) or more than L; n_mels > 384; eps <= 0; tables that do not fit 160 KB of LDS
+ *   (n_fft 2048 fits in both modes, 4096 in neither).
+ *
+ * mmx_wave_sums: one pass over the same pair ->
+ *   out   f64 [B][7] = sum x, sum y, sum x^2, sum y^2, sum x y, sum |x - y|, sum (x - y)^2 over the clip's lens[b] samples, in fp64
+ *         (4096 samples per workgroup in a fixed tree, then per clip in workgroup order by the finishing launch);
+ *   clip  > 0: x is first limited to [-clip, clip] (the extractor clips its reconstruction to +-1); 0: x as it is;
+ *   work  f64 [B][cap][7], cap >= ceil(L / 4096): scratch.
+ *   L1, MSE, SNR and SI-SDR follow from the seven sums (mmx/metrics.py, on the device). */
+int mmx_spec_dist(const float* x, int64_t x_bs, const float* y, int64_t y_bs, int L, int B, const int32_t* lens, const int32_t* h_lens,
+                  const void* basis, const void* filt, int n_fft, int n_mels, double eps, double pow, double* work, int cap,
+                  double* out, hipStream_t stream);
+int mmx_wave_sums(const float* x, int64_t x_bs, const float* y, int64_t y_bs, int L, int B, const int32_t* lens, float clip, double* work,
+                  int cap, double* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

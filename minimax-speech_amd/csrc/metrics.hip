@@ -1,0 +1,364 @@
+// Distances between an estimate x and a reference y, two ragged batches of mono fp32 rows of equal per-clip length, for gfx950:
+// what the reference's DAC-VAE validation reports (dac-vae/loss.py MultiScaleSTFTLoss / MelSpectrogramLoss / L1Loss / SISDRLoss,
+// dac-vae/train.py:706-709) and its latent extractor writes (extract_dac_latents.py:89-95 mse / snr), without a host sync and without
+// a spectrogram in HBM.  mmx/metrics.py builds the tables and states the definitions.
+//
+// mmx_spec_dist, one scale (n_fft, hop = n_fft / 4, torch.stft(center=True) with a periodic Hann window, 1 + len / hop frames):
+//   One workgroup takes 16 frames of one clip through BOTH signals.
+//   stage 0  the sample span under the 16 frames (15 * hop + n_fft samples; the reflection by n_fft / 2 is index arithmetic on the
+//            row) -> LDS as three bf16 planes hi + mid + lo = x.  Hop-sized chunks lie 16 elements (32 B) apart: the 16 frames of an
+//            A fragment start hop samples apart, which at hop = 512 is 1024 B, one bank slot for all of them without the gap; with it
+//            the lanes of every ds_read_b128 group fall on 16 different slots for hop a multiple of 128.
+//   stage 1  DFT as a GEMM on v_mfma_f32_16x16x32_bf16, the mfma6 arithmetic of mel.hip: A = frames (LDS), B = window * cos |
+//            window * sin of all n_fft / 2 + 1 bins, three bf16 planes of the float64 values in mmx_pack_skinny order, every term
+//            pair s + p < 3 kept, fp32 accumulation.
+//            STFT mode: both signals' planes are in LDS at once, a wave's lane holds re / im of the same (frame, bin) for x and y
+//            (one load of the basis fragments serves both), and the distance terms come straight from the accumulators.
+//            Mel mode: x alone goes samples -> magnitudes (LDS, three planes) -> mel = magnitudes x filter planes (stage 2, the
+//            same six-term product), its mel accumulators stay in registers (a wave owns at most 3 of the <= 24 mel tiles) while y
+//            takes the same LDS through the same code; then the terms.  Two signals' sample and magnitude planes of a 2048-point
+//            scale are 2 x (59 + 100) KB, one signal's are 159 KB: staged one after the other they keep 16 frames per workgroup.
+//   Every term from the subtraction on is fp64: |log10 max(a, eps) - log10 max(b, eps)| and |a - b| per (frame, bin or mel), summed
+//   per lane in tile order, across the wave in a fixed butterfly, across the waves in wave order -> work[b][tile][2].  The finishing
+//   launch, one wave per clip, adds the clip's own tiles in a fixed order and divides by frames * bins.
+// mmx_wave_sums: sum x, y, x^2, y^2, xy, |x - y|, (x - y)^2 per clip in fp64 (products of fp32 values are exact in fp64), 4096 samples
+//   per workgroup, the same fixed orders, the same finishing launch.
+// A clip's numbers are a function of its own samples and length: not of the batch, the row index or the grid.
+#include "common.h"
+#include "../../include/mmx_hip.h"
+
+namespace {
+
+constexpr int SD_WAVES = 8, SD_THREADS = SD_WAVES * 64;
+constexpr int SD_GAP = 16;                              // elements between hop-sized chunks of a sample plane
+constexpr int SD_MT = 3;                                // mel tiles per wave: n_mels <= 16 * SD_MT * SD_WAVES = 384
+constexpr int WS_THREADS = 256, WS_PER = 16, WS_CHUNK = WS_THREADS * WS_PER;
+
+struct Bf3 { bf16_t h, m, l; };
+__device__ __forceinline__ Bf3 split3(float v) {       // the remainders are exact in fp32
+    Bf3 o;
+    o.h = f2bf(v);
+    v -= bf2f(o.h);
+    o.m = f2bf(v);
+    v -= bf2f(o.m);
+    o.l = f2bf(v);
+    return o;
+}
+
+__device__ __forceinline__ short8_t ld8(const bf16_t* p) { return *reinterpret_cast<const short8_t*>(p); }
+
+// six bf16 MFMAs = every term (a plane s) x (b plane p) with s + p < 3, smallest terms first (mel.hip)
+__device__ __forceinline__ float4_t mfma6(const short8_t (&a)[3], const short8_t (&b)[3], float4_t c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
+    return c;
+}
+
+__host__ __device__ __forceinline__ int sd_frames(int len, int hop) { return 1 + len / hop; }
+// elements of one sample plane: the span of 16 frames with its gaps
+__host__ __device__ __forceinline__ int sd_plane(int n_fft, int hop) {
+    const int S = 15 * hop + n_fft;
+    return S + SD_GAP * ((S + hop - 1) / hop);
+}
+__host__ __device__ __forceinline__ size_t sd_lds(int n_fft, int nbp, bool mel) {
+    const size_t planes = (size_t)3 * sd_plane(n_fft, n_fft / 4) * sizeof(bf16_t);
+    return (mel ? planes + (size_t)3 * 16 * (nbp + 8) * sizeof(bf16_t) : 2 * planes) + SD_WAVES * 2 * sizeof(double);
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);              // every lane ends with the same bits
+    return v;
+}
+
+struct Dist {
+    double lg = 0.0, mg = 0.0;
+    __device__ __forceinline__ void add(float a, float b, double eps) {
+        const double da = (double)a, db = (double)b;
+        lg += fabs(log10(fmax(da, eps)) - log10(fmax(db, eps)));
+        mg += fabs(da - db);
+    }
+};
+
+// stage 0: the span of the tile's 16 frames, first = t0 * hop - n_fft / 2 on the unpadded row -> three planes
+__device__ __forceinline__ void sd_stage(const float* __restrict__ x, int len, long first, int S, int hop, int SP, bf16_t* xs, int tid) {
+    for (int q = tid; q < S; q += SD_THREADS) {
+        long i = first + q;
+        if (i < 0) i = -i;
+        if (i >= len) i = 2L * (len - 1) - i;
+        // beyond one reflection: only frames past the clip's last reach there, and those enter no sum
+        const float v = (i >= 0 && i < len) ? x[i] : 0.f;
+        const Bf3 s = split3(v);
+        const int p = q + SD_GAP * (q / hop);
+        xs[p] = s.h;
+        xs[SP + p] = s.m;
+        xs[2 * SP + p] = s.l;
+    }
+}
+
+// basis: [3 planes][2 * nbp / 16 tiles][n_fft / 32][64][8], tile 2j = window * cos of bins 16j .. 16j + 15, tile 2j + 1 = window * sin
+// filt : [3 planes][mp / 16 tiles][nbp / 32][64][8]
+// work : [B][cap][2] (sum of the log terms, sum of the magnitude terms) of the clip's tile blockIdx.x
+template <bool MEL>
+__global__ __launch_bounds__(SD_THREADS) void spec_dist_kernel(const float* __restrict__ x, long x_bs, const float* __restrict__ y, long y_bs,
+                                                              int L, const int* __restrict__ lens, const bf16_t* __restrict__ basis,
+                                                              const bf16_t* __restrict__ filt, int n_fft, int nbp, int ncols, int mp,
+                                                              double eps, double* __restrict__ work, int cap) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int hop = n_fft / 4;
+    const int S = 15 * hop + n_fft, SP = sd_plane(n_fft, hop);
+    const int MS = nbp + 8;                             // magnitude row stride: 16-byte aligned rows, 4 banks apart
+    double* red = reinterpret_cast<double*>(smem);      // [SD_WAVES][2]
+    bf16_t* xs = reinterpret_cast<bf16_t*>(smem + SD_WAVES * 2 * sizeof(double));   // [3][SP]
+    bf16_t* ys = xs + 3 * SP;                           // STFT mode: [3][SP] of y;  mel mode: the magnitudes [3][16][MS]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int g = lane >> 4, l16 = lane & 15;
+    const int b = blockIdx.y, t0 = blockIdx.x * 16;
+    const int len = lens ? min(lens[b], L) : L;
+    const int Tb = sd_frames(len, hop);
+    if (len <= n_fft / 2 || t0 >= Tb) return;           // (the entry point refuses such a length) / a tile of padding frames
+    const long first = (long)t0 * hop - n_fft / 2;
+    const int nkt = n_fft / 32;
+    const long PB = (long)2 * nbp * n_fft;              // elements per basis plane
+    const bf16_t* xa = xs + l16 * (hop + SD_GAP);
+    Dist d;
+
+    if constexpr (!MEL) {
+        sd_stage(x + (long)b * x_bs, len, first, S, hop, SP, xs, tid);
+        sd_stage(y + (long)b * y_bs, len, first, S, hop, SP, ys, tid);
+        __syncthreads();
+        const bf16_t* ya = ys + l16 * (hop + SD_GAP);
+        for (int j = wv; j < nbp / 16; j += SD_WAVES) {
+            float4_t rx = {0.f, 0.f, 0.f, 0.f}, ix = rx, ry = rx, iy = rx;
+            const bf16_t* wc = basis + (long)(2 * j) * nkt * 512 + lane * 8;
+            const bf16_t* ws = wc + (long)nkt * 512;
+            for (int kt = 0; kt < nkt; ++kt) {
+                const int o = kt * 32 + g * 8, off = o + SD_GAP * (o / hop);
+                short8_t a[3], e[3], c[3], s[3];
+#pragma unroll
+                for (int p = 0; p < 3; ++p) {
+                    a[p] = ld8(xa + p * SP + off);
+                    e[p] = ld8(ya + p * SP + off);
+                    c[p] = ld8(wc + p * PB + (long)kt * 512);
+                    s[p] = ld8(ws + p * PB + (long)kt * 512);
+                }
+                rx = mfma6(a, c, rx);
+                ix = mfma6(a, s, ix);
+                ry = mfma6(e, c, ry);
+                iy = mfma6(e, s, iy);
+            }
+            // C layout: lane (g, l16) holds frames 4g .. 4g + 3 of bin 16j + l16
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (j * 16 + l16 < ncols && t0 + 4 * g + r < Tb)
+                    d.add(sqrtf(rx[r] * rx[r] + ix[r] * ix[r]), sqrtf(ry[r] * ry[r] + iy[r] * iy[r]), eps);
+        }
+    } else {
+        bf16_t* mg = ys;
+        const int nk2 = nbp / 32, mtiles = mp / 16;
+        const long PF = (long)mp * nbp;
+        const bf16_t* ma = mg + l16 * MS + g * 8;
+        float4_t mx[SD_MT];
+#pragma unroll 1
+        for (int sig = 0; sig < 2; ++sig) {             // the estimate, then the reference, through the same LDS and the same code
+            sd_stage(sig ? y + (long)b * y_bs : x + (long)b * x_bs, len, first, S, hop, SP, xs, tid);
+            __syncthreads();                            // also: every wave has read the first signal's magnitudes
+            for (int j = wv; j < nbp / 16; j += SD_WAVES) {
+                float4_t re = {0.f, 0.f, 0.f, 0.f}, im = re;
+                const bf16_t* wc = basis + (long)(2 * j) * nkt * 512 + lane * 8;
+                const bf16_t* ws = wc + (long)nkt * 512;
+#pragma unroll 2
+                for (int kt = 0; kt < nkt; ++kt) {
+                    const int o = kt * 32 + g * 8, off = o + SD_GAP * (o / hop);
+                    short8_t a[3], c[3], s[3];
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) {
+                        a[p] = ld8(xa + p * SP + off);
+                        c[p] = ld8(wc + p * PB + (long)kt * 512);
+                        s[p] = ld8(ws + p * PB + (long)kt * 512);
+                    }
+                    re = mfma6(a, c, re);
+                    im = mfma6(a, s, im);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const Bf3 m3 = split3(sqrtf(re[r] * re[r] + im[r] * im[r]));
+                    bf16_t* dst = mg + (4 * g + r) * MS + j * 16 + l16;
+                    dst[0] = m3.h;
+                    dst[16 * MS] = m3.m;
+                    dst[32 * MS] = m3.l;
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < SD_MT; ++i) {
+                const int mt = wv + i * SD_WAVES;
+                if (mt >= mtiles) continue;             // uniform over the wave
+                float4_t acc = {0.f, 0.f, 0.f, 0.f};
+                const bf16_t* wf = filt + (long)mt * nk2 * 512 + lane * 8;
+#pragma unroll 2
+                for (int kt = 0; kt < nk2; ++kt) {
+                    short8_t a[3], f[3];
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) {
+                        a[p] = ld8(ma + p * 16 * MS + kt * 32);
+                        f[p] = ld8(wf + p * PF + (long)kt * 512);
+                    }
+                    acc = mfma6(a, f, acc);
+                }
+                if (sig == 0) {
+                    mx[i] = acc;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (mt * 16 + l16 < ncols && t0 + 4 * g + r < Tb) d.add(mx[i][r], acc[r], eps);
+                }
+            }
+        }
+    }
+
+    const double sl = wave_sum_f64(d.lg), sm = wave_sum_f64(d.mg);
+    if (lane == 0) {
+        red[2 * wv] = sl;
+        red[2 * wv + 1] = sm;
+    }
+    __syncthreads();
+    if (tid < 2) {
+        double a = 0.0;
+        for (int w = 0; w < SD_WAVES; ++w) a += red[2 * w + tid];
+        work[((long)b * cap + blockIdx.x) * 2 + tid] = a;
+    }
+}
+
+// One wave per clip: the clip's first `tiles` rows of work[b][cap][NV] added - lane l takes rows l, l + 64, .. in order, then the
+// butterfly - so the order depends on the clip's own tile count alone.  Every lane returns the sums.
+template <int NV>
+__device__ __forceinline__ void clip_sums(const double* __restrict__ w, int tiles, int lane, double (&s)[NV]) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) s[k] = 0.0;
+    for (int i = lane; i < tiles; i += 64) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) s[k] += w[(long)i * NV + k];
+    }
+#pragma unroll
+    for (int k = 0; k < NV; ++k) s[k] = wave_sum_f64(s[k]);
+}
+
+__global__ __launch_bounds__(64) void spec_finish_kernel(const double* __restrict__ work, int cap, const int* __restrict__ lens, int L,
+                                                        int n_fft, int ncols, double pw, double* __restrict__ out) {
+    const int lane = threadIdx.x, b = blockIdx.x, hop = n_fft / 4;
+    const int len = lens ? min(lens[b], L) : L;
+    const int T = sd_frames(max(len, 0), hop);
+    double s[2];
+    clip_sums<2>(work + (long)b * cap * 2, min(cap, (T + 15) / 16), lane, s);
+    if (lane == 0) {
+        const double den = (double)T * (double)ncols;
+        out[2 * b] = pw * s[0] / den;                   // log10(v^pow) = pow log10(v): v >= eps > 0
+        out[2 * b + 1] = s[1] / den;
+    }
+}
+
+__global__ __launch_bounds__(WS_THREADS) void wave_sums_kernel(const float* __restrict__ x, long x_bs, const float* __restrict__ y, long y_bs,
+                                                              int L, const int* __restrict__ lens, float clip, double* __restrict__ work,
+                                                              int cap) {
+    __shared__ double red[WS_THREADS / 64][7];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.y;
+    const int len = lens ? max(0, min(lens[b], L)) : L;
+    const long j0 = (long)blockIdx.x * WS_CHUNK;
+    if (j0 >= len) return;                              // uniform over the workgroup
+    const float* xr = x + (long)b * x_bs;
+    const float* yr = y + (long)b * y_bs;
+    double s[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+    for (int r = 0; r < WS_PER; ++r) {
+        const long j = j0 + tid + r * WS_THREADS;
+        if (j < len) {
+            float xe = xr[j];
+            if (clip > 0.f) xe = fminf(fmaxf(xe, -clip), clip);
+            const double dx = (double)xe, dy = (double)yr[j], df = dx - dy;
+            s[0] += dx;
+            s[1] += dy;
+            s[2] += dx * dx;
+            s[3] += dy * dy;
+            s[4] += dx * dy;
+            s[5] += fabs(df);
+            s[6] += df * df;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        const double v = wave_sum_f64(s[k]);
+        if (lane == 0) red[wv][k] = v;
+    }
+    __syncthreads();
+    if (tid < 7) {
+        double a = 0.0;
+        for (int w = 0; w < WS_THREADS / 64; ++w) a += red[w][tid];
+        work[((long)b * cap + blockIdx.x) * 7 + tid] = a;
+    }
+}
+
+__global__ __launch_bounds__(64) void wave_finish_kernel(const double* __restrict__ work, int cap, const int* __restrict__ lens, int L,
+                                                        double* __restrict__ out) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int len = lens ? max(0, min(lens[b], L)) : L;
+    double s[7];
+    clip_sums<7>(work + (long)b * cap * 7, (int)min((long)cap, ((long)len + WS_CHUNK - 1) / WS_CHUNK), lane, s);
+    if (lane < 7) {
+        double v = s[0];
+#pragma unroll
+        for (int k = 1; k < 7; ++k) v = lane == k ? s[k] : v;
+        out[7 * b + lane] = v;
+    }
+}
+
+}  // namespace
+
+extern "C" int mmx_spec_dist(const float* x, int64_t x_bs, const float* y, int64_t y_bs, int L, int B, const int32_t* lens,
+                             const int32_t* h_lens, const void* basis, const void* filt, int n_fft, int n_mels, double eps, double pow,
+                             double* work, int cap, double* out, hipStream_t stream) {
+    MMX_CHECK_ARG(x && y && basis && work && out && B > 0 && B <= 65535 && L > 0 && x_bs >= L && y_bs >= L);
+    MMX_CHECK_ARG(n_fft >= 32 && n_fft % 32 == 0 && n_fft <= (1 << 20) && (!lens == !h_lens) && eps > 0.0);
+    MMX_CHECK_ARG(n_mels >= 0 && n_mels <= 16 * SD_MT * SD_WAVES && (!n_mels == !filt));
+    const int hop = n_fft / 4;
+    for (int b = 0; b < B; ++b) {
+        const int len = h_lens ? h_lens[b] : L;
+        MMX_CHECK_ARG(len > n_fft / 2 && len <= L);     // the reflection reads sample n_fft / 2
+    }
+    MMX_CHECK_ARG(cap >= (sd_frames(L, hop) + 15) / 16);
+    const int n_bins = n_fft / 2 + 1, nbp = (n_bins + 31) / 32 * 32, mp = (n_mels + 15) / 16 * 16;
+    const size_t lds = sd_lds(n_fft, nbp, n_mels > 0);
+    MMX_CHECK_ARG(lds <= 160 * 1024);
+    const int tiles = (sd_frames(L, hop) + 15) / 16;
+    const dim3 grid(tiles, B), block(SD_THREADS);
+    if (n_mels > 0) {
+        MMX_LDS_OPT_IN(spec_dist_kernel<true>, lds);
+        hipLaunchKernelGGL(spec_dist_kernel<true>, grid, block, lds, stream, x, (long)x_bs, y, (long)y_bs, L, lens, (const bf16_t*)basis,
+                           (const bf16_t*)filt, n_fft, nbp, n_mels, mp, eps, work, cap);
+    } else {
+        MMX_LDS_OPT_IN(spec_dist_kernel<false>, lds);
+        hipLaunchKernelGGL(spec_dist_kernel<false>, grid, block, lds, stream, x, (long)x_bs, y, (long)y_bs, L, lens, (const bf16_t*)basis,
+                           (const bf16_t*)nullptr, n_fft, nbp, n_bins, mp, eps, work, cap);
+    }
+    MMX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(spec_finish_kernel, dim3(B), dim3(64), 0, stream, work, cap, lens, L, n_fft, n_mels > 0 ? n_mels : n_bins, pow, out);
+    MMX_LAUNCH_CHECK();
+    return MMX_OK;
+}
+
+extern "C" int mmx_wave_sums(const float* x, int64_t x_bs, const float* y, int64_t y_bs, int L, int B, const int32_t* lens, float clip,
+                             double* work, int cap, double* out, hipStream_t stream) {
+    MMX_CHECK_ARG(x && y && work && out && B > 0 && B <= 65535 && L > 0 && x_bs >= L && y_bs >= L && clip >= 0.f);
+    const long chunks = ((long)L + WS_CHUNK - 1) / WS_CHUNK;
+    MMX_CHECK_ARG(cap >= chunks);
+    hipLaunchKernelGGL(wave_sums_kernel, dim3((unsigned)chunks, B), dim3(WS_THREADS), 0, stream, x, (long)x_bs, y, (long)y_bs, L, lens, clip,
+                       work, cap);
+    MMX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(wave_finish_kernel, dim3(B), dim3(64), 0, stream, work, cap, lens, L, out);
+    MMX_LAUNCH_CHECK();
+    return MMX_OK;
+}

@@ -70,6 +70,36 @@ def latent_records(model, audios, sample_rate: int, original_paths: List[str] = 
     return recs
 
 
+@torch.inference_mode()
+def reconstruction_info(model, audio, sample_rate: int, original_path: str = "") -> Dict:
+    """How well does this checkpoint reconstruct one mono waveform?  The comparison half of extract_dac_latents.py (:57-106
+    decode_and_save_sample, without its file writes): the clip is clamped to [-1, 1] and encoded unpadded as latent_record does,
+    decoded, the reconstruction limited to [-1, 1] and both trimmed to the shorter; returns the `info` dict of :98-106
+    (`mse`, `snr` as numpy computes them there) plus mmx.metrics.audio_distance's values (mel, stft, l1, sisdr_db) and the
+    reconstructed audio (`reconstructed`, a device tensor [n]).  One encode, one decode and one set of metric launches; the
+    first host sync is the read-back of the six numbers at the end."""
+    from mmx import metrics
+    if sample_rate != model.sample_rate:
+        raise ValueError(f"audio must be resampled to {model.sample_rate} Hz first (got {sample_rate})")
+    audio = torch.as_tensor(np.asarray(audio) if not torch.is_tensor(audio) else audio).float().reshape(-1)
+    dev = next(model.parameters()).device
+    x = torch.clamp(audio.to(dev).reshape(1, 1, -1), -1.0, 1.0)
+    z, _, _ = model.encode(x, sample_rate)
+    rec = model.decode(z).reshape(-1)
+    n = min(x.shape[-1], rec.numel())
+    d = metrics.audio_distance(rec[None, :n], x.reshape(1, -1)[:, :n], sample_rate, clip=1.0)
+    vals = torch.stack([d[k][0] for k in ("mse", "snr_db", "mel", "stft", "l1", "sisdr_db")]).cpu().tolist()     # the one sync
+    return {
+        "original_path": original_path,
+        "original_duration": audio.numel() / sample_rate,
+        "reconstructed_duration": rec.numel() / sample_rate,
+        "latent_shape": list(z.squeeze(0).shape),
+        "compression_ratio": x.shape[-1] // z.shape[-1],
+        "mse": vals[0], "snr": vals[1], "mel": vals[2], "stft": vals[3], "l1": vals[4], "sisdr_db": vals[5],
+        "reconstructed": torch.clamp(rec, -1.0, 1.0),
+    }
+
+
 def save_latents(model, audios, sample_rate: int, audio_paths: List[str]) -> List[str]:
     """latent_records, each written as `<audio stem>_latent2x.pt` next to its audio file; returns the paths written."""
     outs = []

@@ -1,0 +1,216 @@
+"""Audio distances on the device (csrc/metrics.hip mmx_spec_dist / mmx_wave_sums, mmx/metrics.py, dac-vae/loss.py,
+latents.reconstruction_info) against the float64 yardstick and fixtures of tests/test_metrics_host.py.
+
+Tolerances.  Two caps are conditions of use, not measurements: a distance of 0.1 or more (`codec`, `half`, `silent`) is quoted to
+four digits, so |device - float64| <= 1e-4 * float64; a difference the size of a build-to-build one (`near`: 2.6e-4 mel, 6.5e-4
+STFT) to two, so <= 1e-2 * float64.  The kernel is deterministic; the test constants below are 4 x the worst error measured on an
+MI355X per class of fixture (DESIGN.md §4.4 lists them), the margin being for clips other than these, and never above the caps."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import test_metrics_host as H
+from mmx import metrics as M
+from mmx._lib import MmxError
+
+pytestmark = pytest.mark.gpu
+
+RATE = H.RATE
+CAP_BIG, CAP_NEAR = 1e-4, 1e-2
+# worst relative errors measured on an MI355X over everything `close` checks below: 3.43e-7 where the distance is >= 0.1 (the
+# magnitude term of `codec` at 2048 / 320 mels; the log terms stay below 5e-8), 3.96e-5 on `near` (n_fft 1024, STFT)
+TOL_BIG, TOL_NEAR = min(CAP_BIG, 4 * 3.43e-7), min(CAP_NEAR, 4 * 3.96e-5)
+SCALES = [(32, 5, 1.0, 1.0, 0.0),        # one K tile, 17 bins in one tile pair, 11 padded mel columns
+          (2048, 320, 1.0, 1.0, 0.0),    # 64 K tiles, bin 1024 alone in the 65th bin tile, 20 mel tiles
+          (1024, 0, 2.0, 1.0, 1.0),      # the two STFT scales of the validation step: pow 2, both weights
+          (2048, 0, 2.0, 1.0, 1.0)]
+PAIRS = [("codec", RATE), ("half", RATE), ("near", RATE)] + [("codec", n) for n in H.EDGE_LENGTHS]
+
+
+def dev(x):
+    return x.cuda()
+
+
+WORST = {"big": 0.0, "near": 0.0}
+
+
+def close(kind, what, got, want):
+    """Prints the figure, then holds it to the class's tolerance."""
+    rel = abs(got - want) / want
+    WORST[kind] = max(WORST[kind], rel)
+    print(f"{what}: device {got:.9g} float64 {want:.9g} rel {rel:.2e}   (worst so far: {WORST['big']:.2e} >= 0.1, {WORST['near']:.2e} near)")
+    assert rel <= (TOL_NEAR if kind == "near" else TOL_BIG), (what, got, want)
+
+
+@pytest.mark.parametrize("n_fft,n_mels,pw,log_w,mag_w", SCALES)
+def test_one_scale_against_float64(n_fft, n_mels, pw, log_w, mag_w):
+    """Every fixture pair and every edge length as ONE ragged batch through one scale (solo runs give the same bits: below)."""
+    est = [dev(H.clip(name)[:n]) for name, n in PAIRS]
+    ref = [dev(H.clip("ref")[:n]) for _, n in PAIRS]
+    x, y, lens = M._pair(est, ref, None)
+    got = M.spec_dist(x, y, lens, RATE, n_fft, n_mels, pow=pw).cpu()
+    for i, (name, n) in enumerate(PAIRS):
+        want = H.spec_ref(H.clip(name)[:n], H.clip("ref")[:n], n_fft, n_mels, pow=pw)
+        w = log_w * want[0] + mag_w * want[1]
+        kind = "near" if name == "near" else "big"
+        assert kind == "near" or w >= 0.1 / 7, (name, n, w)          # a scale's share of a distance >= 0.1
+        close(kind, f"n_fft {n_fft} mels {n_mels} {name}[:{n}]", float(log_w * got[i, 0] + mag_w * got[i, 1]), w)
+        if mag_w == 0.0 and kind == "big":
+            # the magnitude term the weights leave out is computed all the same; for `near` at 5 mels it is 2e-8, below what fp32
+            # magnitudes resolve, and no distance is quoted from it
+            close(kind, f"n_fft {n_fft} mels {n_mels} {name}[:{n}] magnitude term", float(got[i, 1]), want[1])
+
+
+def test_whole_distances_against_float64():
+    est = [dev(H.clip(k)) for k in ("codec", "half", "near", "silent")]
+    ref = [dev(H.clip("ref"))] * 4
+    d = {k: v.cpu() for k, v in M.audio_distance(est, ref, RATE).items()}
+    for i, name in enumerate(("codec", "half", "near", "silent")):
+        for key, want in (("mel", H.mel_ref(name, "ref")), ("stft", H.stft_ref(name, "ref"))):
+            close("near" if name == "near" else "big", f"{key} {name}", float(d[key][i]), want)
+    close("big", "mel half against 7 log10 2", float(d["mel"][1]), 7 * math.log10(2.0))
+    # defaults of the public functions: loss.py's own (STFT windows 2048 and 512)
+    close("big", "stft_distance defaults", float(M.stft_distance([est[0]], [ref[0]])[0]), H.stft_ref("codec", "ref", RATE, (2048, 512)))
+
+
+def test_exact_zeros_and_the_clamp():
+    x, z = dev(H.clip("codec")), dev(H.clip("silent"))
+    d = M.audio_distance([x, z], [x, z], RATE)
+    for k in ("mel", "stft", "l1", "mse"):
+        assert d[k].tolist() == [0.0, 0.0], k
+    assert float(d["sisdr_db"][0]) == math.inf
+    var = float(np.var(H.clip("codec").double().numpy()))
+    assert abs(float(d["snr_db"][0]) - 10 * math.log10(var / 1e-10)) < 1e-9
+    # one side entirely at the clamp
+    for n_fft, n_mels, pw, log_w, mag_w in SCALES:
+        got = M.spec_dist(z[None], dev(H.clip("ref"))[None], None, RATE, n_fft, n_mels, pow=pw).cpu()[0]
+        want = H.spec_ref(H.clip("silent"), H.clip("ref"), n_fft, n_mels, pow=pw)
+        for what, g, w in zip(("log", "magnitude"), got.tolist(), want):
+            close("big", f"n_fft {n_fft} mels {n_mels} silent, {what} term", g, w)
+
+
+def test_waveform_sums_and_metrics():
+    names = ("codec", "half", "near")
+    est, ref = [dev(H.clip(k)) for k in names], [dev(H.clip("ref"))] * 3
+    d = {k: v.cpu() for k, v in M.waveform_distance(est, ref).items()}
+    for i, name in enumerate(names):
+        want = H.wave_ref(H.clip(name), H.clip("ref"))
+        for k in ("l1", "mse", "snr_db"):
+            assert abs(float(d[k][i]) - want[k]) <= 1e-12 * abs(want[k]), (name, k, float(d[k][i]), want[k])
+    i = names.index("near")
+    want = H.wave_ref(H.clip("near"), H.clip("ref"))["sisdr_db"]
+    print(f"sisdr near: device {float(d['sisdr_db'][i]):.9f} float64 two-pass {want:.9f}")
+    assert abs(want - 87.27) < 0.2 and abs(float(d["sisdr_db"][i]) - want) <= 1e-4
+    want = H.wave_ref(H.clip("codec"), H.clip("ref"))["sisdr_db"]
+    assert abs(float(d["sisdr_db"][0]) - want) <= 1e-4
+    s = M.wave_sums(est[0][None], ref[0][None]).cpu().numpy()[0]
+    np.testing.assert_allclose(s, H.sums_np(H.clip("codec"), H.clip("ref")), rtol=1e-12, atol=1e-12)
+    # the clip to +-1, on a clip scaled to peak 1.5 (a ragged length: the last chunk is partial)
+    loud = (H.clip("ref") * (1.5 / H.clip("ref").abs().max()))[:23001]
+    assert int((loud.abs() > 1).sum()) > 100
+    got = {k: float(v[0]) for k, v in M.waveform_distance([dev(loud)], [dev(H.clip("ref")[:23001])], clip=1.0).items()}
+    want = H.wave_ref(loud, H.clip("ref")[:23001], clipv=1.0)
+    unclipped = H.wave_ref(loud, H.clip("ref")[:23001])
+    for k in ("l1", "mse", "snr_db"):
+        assert abs(got[k] - want[k]) <= 1e-12 * abs(want[k]) and abs(want[k] - unclipped[k]) > 1e-6 * abs(want[k]), k
+    assert abs(got["sisdr_db"] - want["sisdr_db"]) <= 1e-4
+
+
+def test_ragged_batch_equals_solo_runs_bit_for_bit():
+    """Clips of 24000, 1025, 4097 and 20000 samples as one padded batch: at hop 8 the 1025-sample member owns 9 of the batch's 188
+    tiles, the rest of its row is padding tiles."""
+    lengths = (RATE, 1025, 4097, 20000)
+    est = [dev(H.clip("codec")[:n]) for n in lengths]
+    ref = [dev(H.clip("ref")[:n]) for n in lengths]
+    batch = M.audio_distance(est, ref, RATE, clip=1.0)
+    x, y, lens = M._pair(est, ref, None)
+    # the same members behind other rows and other padding: a padded tensor with lens, rows reversed
+    rev = M.audio_distance(x.flip(0).contiguous(), y.flip(0).contiguous(), RATE, lens=lens[::-1], clip=1.0)
+    for i in range(len(lengths)):
+        solo = M.audio_distance([est[i]], [ref[i]], RATE, clip=1.0)
+        for k in batch:
+            assert torch.equal(batch[k][i], solo[k][0]), (k, lengths[i])
+            assert torch.equal(rev[k][len(lengths) - 1 - i], solo[k][0]), (k, lengths[i])
+
+
+def test_refusals():
+    short, ok = dev(H.clip("ref")[:1024]), dev(H.clip("ref")[:1025])
+    with pytest.raises(MmxError):
+        M.spec_dist(short[None], short[None], None, RATE, 2048)
+    with pytest.raises(MmxError):                         # one short member of a batch refuses the batch
+        M.stft_distance([ok, short], [ok, short], window_lengths=(2048,))
+    with pytest.raises(MmxError):
+        M.spec_dist(ok[None], ok[None], None, RATE, 48)   # not a multiple of 32
+    with pytest.raises(MmxError):
+        M.spec_dist(dev(H.clip("ref"))[None], dev(H.clip("ref"))[None], None, RATE, 4096)      # its planes do not fit LDS
+    with pytest.raises(ValueError):
+        M.audio_distance([ok], [short], RATE)
+    with pytest.raises(ValueError):
+        M.mel_distance(ok[None], short[None], RATE)
+    # the entry point itself: MMX_EARG (-1) for the short clip, for a length that host and device disagree on being given, and for
+    # an n_fft that is no multiple of 32; `out` keeps its bits (nothing ran)
+    from mmx._lib import _p, i64, load, stream
+    import ctypes as C
+    basis, _ = M._device_tables(RATE, 2048, 0, 0.0, None, ok.device)
+    work, out = torch.zeros(1, 1, 2, dtype=torch.float64, device="cuda"), torch.full((1, 2), -7.0, dtype=torch.float64, device="cuda")
+
+    def raw(x, n, n_fft, h_lens=None, d_lens=None):
+        return load().mmx_spec_dist(_p(x), i64(n), _p(x), i64(n), n, 1, _p(d_lens), h_lens, _p(basis), None, n_fft, 0, C.c_double(1e-5),
+                                    C.c_double(1.0), _p(work), 1, _p(out), stream())
+    assert raw(short, 1024, 2048) == -1
+    assert raw(ok, 1025, 2048, (C.c_int32 * 1)(1024), torch.tensor([1024], dtype=torch.int32, device="cuda")) == -1
+    assert raw(ok, 1025, 2048, (C.c_int32 * 1)(1025), None) == -1
+    assert raw(ok, 1025, 48) == -1
+    torch.cuda.synchronize()
+    assert out.tolist() == [[-7.0, -7.0]]
+    assert raw(ok, 1025, 2048) == 0 and out.tolist() == [[0.0, 0.0]]                  # the shortest legal clip runs
+
+
+def test_dropin_losses_return_the_batch_mean():
+    import loss as DL
+    est = torch.stack([dev(H.clip(k)) for k in ("codec", "half", "near")])[:, None]      # [3, 1, T]
+    ref = torch.stack([dev(H.clip("ref"))] * 3)[:, None]
+    d = M.audio_distance(est, ref, RATE)
+    assert torch.equal(DL.MelSpectrogramLoss(sample_rate=RATE)(est, ref), d["mel"].mean())
+    assert torch.equal(DL.MultiScaleSTFTLoss(window_lengths=[1024, 2048])(est, ref), d["stft"].mean())
+    assert torch.equal(DL.L1Loss()(est, ref), d["l1"].mean())
+    assert torch.equal(DL.SISDRLoss()(ref, est), -d["sisdr_db"].mean())                  # loss.py:95-96: x is the reference there
+    assert torch.equal(DL.SISDRLoss(reduction="none")(ref, est), -d["sisdr_db"])
+
+    class Sig:
+        def __init__(self, a):
+            self.audio_data, self.sample_rate = a, RATE
+    assert torch.equal(DL.MelSpectrogramLoss()(Sig(est), Sig(ref)), d["mel"].mean())
+    x, y = H.clip("codec").double().numpy(), H.clip("ref").double().numpy()
+    plain = -10 * np.log10((x ** 2).sum() / ((y - x) ** 2).sum() + 1e-8)                 # scaling=False, zero_mean=False; x the reference
+    got = float(DL.SISDRLoss(scaling=False, zero_mean=False)(est[:1], ref[:1]))
+    assert abs(got - plain) <= 1e-9
+
+
+def test_reconstruction_info_on_the_synthetic_checkpoint(golden_dir):
+    import latents
+    import test_dropin_api as D
+    from oracle import weights as W
+    dac = D.build_dac(80)
+    dac.load_state_dict(W.synth_state_dict({**D._ref(golden_dir, "dac80"), **D._ref(golden_dir, "dacenc")}, 7), strict=True)
+    dac.to("cuda").float_parity()
+    wav = np.load(os.path.join(golden_dir, "dacenc.npz"))["wav_11000"].reshape(-1)
+    info = latents.reconstruction_info(dac, wav, 24000, "spk1/utt.wav")
+    assert set(info) == {"original_path", "original_duration", "reconstructed_duration", "latent_shape", "compression_ratio", "mse", "snr",
+                         "mel", "stft", "l1", "sisdr_db", "reconstructed"}
+    assert info["original_path"] == "spk1/utt.wav" and info["latent_shape"] == [80, 23] and info["compression_ratio"] == 11000 // 23
+    assert info["original_duration"] == 11000 / 24000 and info["reconstructed_duration"] == 23 * 480 / 24000
+    rec = info["reconstructed"].cpu().double().numpy()
+    assert rec.shape == (23 * 480,) and np.abs(rec).max() <= 1.0
+    orig = np.clip(wav.astype(np.float32), -1.0, 1.0).astype(np.float64)
+    n = min(len(orig), len(rec))
+    mse = np.mean((orig[:n] - rec[:n]) ** 2)
+    snr = 10 * np.log10(np.var(orig[:n]) / (mse + 1e-10))
+    assert abs(info["mse"] - mse) <= 1e-12 * mse and abs(info["snr"] - snr) <= 1e-9
+    assert info["mel"] > 0 and info["stft"] > 0 and math.isfinite(info["sisdr_db"])
+    assert abs(info["l1"] - np.mean(np.abs(orig[:n] - rec[:n]))) <= 1e-12 * info["l1"]
+    with pytest.raises(ValueError, match="resampled"):
+        latents.reconstruction_info(dac, wav, 16000)
