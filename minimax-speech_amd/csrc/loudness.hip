@@ -210,12 +210,6 @@ __global__ __launch_bounds__(64) void kweight_carry_kernel(int L, const int* __r
     if (lane == 0) peak[b] = (float)pk;                                      // exact: the maximum of fp32 values
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);              // every lane ends with the same bits
-    return v;
-}
-
 struct GateArgs {
     double G[MMX_LOUD_MAX_CH];
 };

@@ -4,14 +4,10 @@
 // a spectrogram in HBM.  mmx/metrics.py builds the tables and states the definitions.
 //
 // mmx_spec_dist, one scale (n_fft, hop = n_fft / 4, torch.stft(center=True) with a periodic Hann window, 1 + len / hop frames):
-//   One workgroup takes 16 frames of one clip through BOTH signals.
+//   One workgroup takes 16 frames of one clip through BOTH signals, on the functions of spec_tile.h.
 //   stage 0  the sample span under the 16 frames (15 * hop + n_fft samples; the reflection by n_fft / 2 is index arithmetic on the
-//            row) -> LDS as three bf16 planes hi + mid + lo = x.  Hop-sized chunks lie 16 elements (32 B) apart: the 16 frames of an
-//            A fragment start hop samples apart, which at hop = 512 is 1024 B, one bank slot for all of them without the gap; with it
-//            the lanes of every ds_read_b128 group fall on 16 different slots for hop a multiple of 128.
-//   stage 1  DFT as a GEMM on v_mfma_f32_16x16x32_bf16, the mfma6 arithmetic of mel.hip: A = frames (LDS), B = window * cos |
-//            window * sin of all n_fft / 2 + 1 bins, three bf16 planes of the float64 values in mmx_pack_skinny order, every term
-//            pair s + p < 3 kept, fp32 accumulation.
+//            row) -> LDS as three bf16 planes hi + mid + lo = x, hop-sized chunks 16 elements apart (the header's GAP).
+//   stage 1  DFT of all n_fft / 2 + 1 bins as the six-term bf16 MFMA product, fp32 accumulation.
 //            STFT mode: both signals' planes are in LDS at once, a wave's lane holds re / im of the same (frame, bin) for x and y
 //            (one load of the basis fragments serves both), and the distance terms come straight from the accumulators.
 //            Mel mode: x alone goes samples -> magnitudes (LDS, three planes) -> mel = magnitudes x filter planes (stage 2, the
@@ -24,7 +20,7 @@
 // mmx_wave_sums: sum x, y, x^2, y^2, xy, |x - y|, (x - y)^2 per clip in fp64 (products of fp32 values are exact in fp64), 4096 samples
 //   per workgroup, the same fixed orders, the same finishing launch.
 // A clip's numbers are a function of its own samples and length: not of the batch, the row index or the grid.
-#include "common.h"
+#include "spec_tile.h"
 #include "../../include/mmx_hip.h"
 
 namespace {
@@ -34,45 +30,12 @@ constexpr int SD_GAP = 16;                              // elements between hop-
 constexpr int SD_MT = 3;                                // mel tiles per wave: n_mels <= 16 * SD_MT * SD_WAVES = 384
 constexpr int WS_THREADS = 256, WS_PER = 16, WS_CHUNK = WS_THREADS * WS_PER;
 
-struct Bf3 { bf16_t h, m, l; };
-__device__ __forceinline__ Bf3 split3(float v) {       // the remainders are exact in fp32
-    Bf3 o;
-    o.h = f2bf(v);
-    v -= bf2f(o.h);
-    o.m = f2bf(v);
-    v -= bf2f(o.m);
-    o.l = f2bf(v);
-    return o;
-}
-
-__device__ __forceinline__ short8_t ld8(const bf16_t* p) { return *reinterpret_cast<const short8_t*>(p); }
-
-// six bf16 MFMAs = every term (a plane s) x (b plane p) with s + p < 3, smallest terms first (mel.hip)
-__device__ __forceinline__ float4_t mfma6(const short8_t (&a)[3], const short8_t (&b)[3], float4_t c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
-    return c;
-}
-
 __host__ __device__ __forceinline__ int sd_frames(int len, int hop) { return 1 + len / hop; }
 // elements of one sample plane: the span of 16 frames with its gaps
-__host__ __device__ __forceinline__ int sd_plane(int n_fft, int hop) {
-    const int S = 15 * hop + n_fft;
-    return S + SD_GAP * ((S + hop - 1) / hop);
-}
+__host__ __device__ __forceinline__ int sd_plane(int n_fft, int hop) { return spec_plane<SD_GAP>(15 * hop + n_fft, hop); }
 __host__ __device__ __forceinline__ size_t sd_lds(int n_fft, int nbp, bool mel) {
     const size_t planes = (size_t)3 * sd_plane(n_fft, n_fft / 4) * sizeof(bf16_t);
     return (mel ? planes + (size_t)3 * 16 * (nbp + 8) * sizeof(bf16_t) : 2 * planes) + SD_WAVES * 2 * sizeof(double);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);              // every lane ends with the same bits
-    return v;
 }
 
 struct Dist {
@@ -83,22 +46,6 @@ struct Dist {
         mg += fabs(da - db);
     }
 };
-
-// stage 0: the span of the tile's 16 frames, first = t0 * hop - n_fft / 2 on the unpadded row -> three planes
-__device__ __forceinline__ void sd_stage(const float* __restrict__ x, int len, long first, int S, int hop, int SP, bf16_t* xs, int tid) {
-    for (int q = tid; q < S; q += SD_THREADS) {
-        long i = first + q;
-        if (i < 0) i = -i;
-        if (i >= len) i = 2L * (len - 1) - i;
-        // beyond one reflection: only frames past the clip's last reach there, and those enter no sum
-        const float v = (i >= 0 && i < len) ? x[i] : 0.f;
-        const Bf3 s = split3(v);
-        const int p = q + SD_GAP * (q / hop);
-        xs[p] = s.h;
-        xs[SP + p] = s.m;
-        xs[2 * SP + p] = s.l;
-    }
-}
 
 // basis: [3 planes][2 * nbp / 16 tiles][n_fft / 32][64][8], tile 2j = window * cos of bins 16j .. 16j + 15, tile 2j + 1 = window * sin
 // filt : [3 planes][mp / 16 tiles][nbp / 32][64][8]
@@ -121,96 +68,49 @@ __global__ __launch_bounds__(SD_THREADS) void spec_dist_kernel(const float* __re
     const int len = lens ? min(lens[b], L) : L;
     const int Tb = sd_frames(len, hop);
     if (len <= n_fft / 2 || t0 >= Tb) return;           // (the entry point refuses such a length) / a tile of padding frames
-    const long first = (long)t0 * hop - n_fft / 2;
+    const long first = (long)t0 * hop - n_fft / 2;      // of the tile's span on the unpadded row
     const int nkt = n_fft / 32;
     const long PB = (long)2 * nbp * n_fft;              // elements per basis plane
-    const bf16_t* xa = xs + l16 * (hop + SD_GAP);
+    const float* xr = x + (long)b * x_bs;
+    const float* yr = y + (long)b * y_bs;
     Dist d;
 
     if constexpr (!MEL) {
-        sd_stage(x + (long)b * x_bs, len, first, S, hop, SP, xs, tid);
-        sd_stage(y + (long)b * y_bs, len, first, S, hop, SP, ys, tid);
+        spec_stage<SD_GAP>(xr, len, first, S, S, 1.f, hop, xs, SP, tid, SD_THREADS);
+        spec_stage<SD_GAP>(yr, len, first, S, S, 1.f, hop, ys, SP, tid, SD_THREADS);
         __syncthreads();
-        const bf16_t* ya = ys + l16 * (hop + SD_GAP);
+        const bf16_t* const sig[2] = {xs, ys};
         for (int j = wv; j < nbp / 16; j += SD_WAVES) {
-            float4_t rx = {0.f, 0.f, 0.f, 0.f}, ix = rx, ry = rx, iy = rx;
-            const bf16_t* wc = basis + (long)(2 * j) * nkt * 512 + lane * 8;
-            const bf16_t* ws = wc + (long)nkt * 512;
-            for (int kt = 0; kt < nkt; ++kt) {
-                const int o = kt * 32 + g * 8, off = o + SD_GAP * (o / hop);
-                short8_t a[3], e[3], c[3], s[3];
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    a[p] = ld8(xa + p * SP + off);
-                    e[p] = ld8(ya + p * SP + off);
-                    c[p] = ld8(wc + p * PB + (long)kt * 512);
-                    s[p] = ld8(ws + p * PB + (long)kt * 512);
-                }
-                rx = mfma6(a, c, rx);
-                ix = mfma6(a, s, ix);
-                ry = mfma6(e, c, ry);
-                iy = mfma6(e, s, iy);
-            }
-            // C layout: lane (g, l16) holds frames 4g .. 4g + 3 of bin 16j + l16
+            float4_t re[2], im[2];
+            spec_dft_tile<2, SD_GAP>(sig, SP, hop, basis, PB, nkt, j, lane, re, im);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (j * 16 + l16 < ncols && t0 + 4 * g + r < Tb)
-                    d.add(sqrtf(rx[r] * rx[r] + ix[r] * ix[r]), sqrtf(ry[r] * ry[r] + iy[r] * iy[r]), eps);
+                    d.add(sqrtf(re[0][r] * re[0][r] + im[0][r] * im[0][r]), sqrtf(re[1][r] * re[1][r] + im[1][r] * im[1][r]), eps);
         }
     } else {
         bf16_t* mg = ys;
-        const int nk2 = nbp / 32, mtiles = mp / 16;
-        const long PF = (long)mp * nbp;
-        const bf16_t* ma = mg + l16 * MS + g * 8;
+        const int mtiles = mp / 16;
+        const bf16_t* const sig[1] = {xs};
         float4_t mx[SD_MT];
 #pragma unroll 1
-        for (int sig = 0; sig < 2; ++sig) {             // the estimate, then the reference, through the same LDS and the same code
-            sd_stage(sig ? y + (long)b * y_bs : x + (long)b * x_bs, len, first, S, hop, SP, xs, tid);
+        for (int s = 0; s < 2; ++s) {                   // the estimate, then the reference, through the same LDS and the same code
+            spec_stage<SD_GAP>(s ? yr : xr, len, first, S, S, 1.f, hop, xs, SP, tid, SD_THREADS);
             __syncthreads();                            // also: every wave has read the first signal's magnitudes
             for (int j = wv; j < nbp / 16; j += SD_WAVES) {
-                float4_t re = {0.f, 0.f, 0.f, 0.f}, im = re;
-                const bf16_t* wc = basis + (long)(2 * j) * nkt * 512 + lane * 8;
-                const bf16_t* ws = wc + (long)nkt * 512;
-#pragma unroll 2
-                for (int kt = 0; kt < nkt; ++kt) {
-                    const int o = kt * 32 + g * 8, off = o + SD_GAP * (o / hop);
-                    short8_t a[3], c[3], s[3];
+                float4_t re[1], im[1];
+                spec_dft_tile<1, SD_GAP>(sig, SP, hop, basis, PB, nkt, j, lane, re, im);
 #pragma unroll
-                    for (int p = 0; p < 3; ++p) {
-                        a[p] = ld8(xa + p * SP + off);
-                        c[p] = ld8(wc + p * PB + (long)kt * 512);
-                        s[p] = ld8(ws + p * PB + (long)kt * 512);
-                    }
-                    re = mfma6(a, c, re);
-                    im = mfma6(a, s, im);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const Bf3 m3 = split3(sqrtf(re[r] * re[r] + im[r] * im[r]));
-                    bf16_t* dst = mg + (4 * g + r) * MS + j * 16 + l16;
-                    dst[0] = m3.h;
-                    dst[16 * MS] = m3.m;
-                    dst[32 * MS] = m3.l;
-                }
+                for (int r = 0; r < 4; ++r)
+                    spec_store3(mg, MS, 4 * g + r, j * 16 + l16, sqrtf(re[0][r] * re[0][r] + im[0][r] * im[0][r]));
             }
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < SD_MT; ++i) {
                 const int mt = wv + i * SD_WAVES;
                 if (mt >= mtiles) continue;             // uniform over the wave
-                float4_t acc = {0.f, 0.f, 0.f, 0.f};
-                const bf16_t* wf = filt + (long)mt * nk2 * 512 + lane * 8;
-#pragma unroll 2
-                for (int kt = 0; kt < nk2; ++kt) {
-                    short8_t a[3], f[3];
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) {
-                        a[p] = ld8(ma + p * 16 * MS + kt * 32);
-                        f[p] = ld8(wf + p * PF + (long)kt * 512);
-                    }
-                    acc = mfma6(a, f, acc);
-                }
-                if (sig == 0) {
+                const float4_t acc = spec_mel_tile(mg, MS, filt, (long)mp * nbp, nbp / 32, mt, lane);
+                if (s == 0) {
                     mx[i] = acc;
                 } else {
 #pragma unroll

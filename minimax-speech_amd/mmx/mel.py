@@ -2,8 +2,9 @@
 
 Reference: speech/matcha/utils/audio.py:45-82 (mel_spectrogram, center=False) and the inference branch of
 cosyvoice/dataset/processor.py:339-392 (extract_reference_mel_from_speech: centre crop, peak normalisation).  The arithmetic is
-one launch of mmx_logmel (csrc/mel.hip); this module builds its tables: the windowed DFT basis and the mel filterbank, both as
-three bf16 planes of their exact values.  There is no CPU fallback: a CPU tensor raises.
+one launch of mmx_logmel (csrc/mel.hip).  This module builds the tables of every spectral front end (that one, s3tok.LogMelW,
+mmx/metrics.py): the windowed DFT basis and the mel filterbank in float64, both as three bf16 planes of their exact values.
+There is no CPU fallback: a CPU tensor raises.
 
 mel_filterbank restates what `librosa.filters.mel` builds with its defaults (htk=False, norm="slaney") from that function's
 published definition; librosa itself is not a dependency (restated seams)."""
@@ -62,7 +63,7 @@ def frames_of(n, n_fft, hop):
     return (n + 2 * pad - n_fft) // hop + 1 if (n > pad and n + 2 * pad >= n_fft) else 0
 
 
-def _planes3(v64):
+def planes3(v64):
     """float64 -> three bf16 terms hi + mid + lo (24 significant bits), round to nearest each."""
     out, r = [], v64
     for _ in range(3):
@@ -70,6 +71,40 @@ def _planes3(v64):
         out.append(t)
         r = r - t.double()
     return out
+
+
+_planes3 = planes3
+
+
+def dft_basis(n_fft, bin0=0, n_bins=None, kp=None):
+    """float64 [2 * (n_bins rounded up to 32), kp] for bins bin0 .. bin0 + n_bins - 1 (None: up to n_fft // 2): bin bin0 + i ->
+    row 32 * (i // 16) + i % 16 = hann[k] cos(2 pi (bin0 + i) k / n_fft), that row + 16 the sine (a 16-row tile pair per 16 bins);
+    the phase reduced exactly in integers; periodic Hann window (torch.hann_window's default) folded in.  kp (None: n_fft) pads
+    the K dimension: columns at and beyond n_fft are zero."""
+    n_bins = n_fft // 2 + 1 - bin0 if n_bins is None else n_bins
+    k = torch.arange(n_fft, dtype=torch.int64)
+    bins = torch.arange(bin0, bin0 + n_bins, dtype=torch.int64)
+    ang = ((bins[:, None] * k[None, :]) % n_fft).double() * (2 * math.pi / n_fft)
+    hann = 0.5 - 0.5 * torch.cos(k.double() * (2 * math.pi / n_fft))
+    i = torch.arange(n_bins)
+    rows = 32 * (i // 16) + i % 16
+    basis = torch.zeros(2 * ops.round_up(n_bins, 32), n_fft if kp is None else kp, dtype=torch.float64)
+    basis[rows, :n_fft] = hann * torch.cos(ang)
+    basis[rows + 16, :n_fft] = hann * torch.sin(ang)
+    return basis
+
+
+def filter_table(fb, bin0, n_bins):
+    """float64 [n_mels rounded up to 16, n_bins rounded up to 32]: columns bin0 .. bin0 + n_bins - 1 of the fp32 filterbank the
+    reference holds, zero padded."""
+    filt = torch.zeros(ops.round_up(fb.shape[0], 16), ops.round_up(n_bins, 32), dtype=torch.float64)
+    filt[:fb.shape[0], :n_bins] = torch.from_numpy(fb[:, bin0:bin0 + n_bins].astype(np.float64))
+    return filt
+
+
+def packed3(m64, dev):
+    """A float64 table -> its three bf16 planes on `dev`, each in mmx_pack_skinny order, one after the other."""
+    return torch.cat([ops.pack_skinny(p.to(dev).contiguous(), dtype=BF16) for p in planes3(m64)])
 
 
 def crop_bounds(n, sample_rate, min_length=0.5, max_length=4.0):
@@ -97,24 +132,76 @@ def prepare_reference(wave, sample_rate, min_length=0.5, max_length=4.0):
     return seg, gain
 
 
-class LogMel:
-    """The device tables of one mel setting (DFT basis planes, filter planes, bin range) and the launch."""
+class _LogMelTables:
+    """What LogMel and s3tok.LogMelW share: one instance per (setting, device) holding the device tables (DFT basis planes,
+    filter planes, bin range), and the plumbing of a call.  A subclass gives _build, frames, its entry point's name, whether that
+    takes a per-member gain, and whether a bf16 result needs the fp32 channel-major one beside it."""
 
-    _cache = {}
+    _entry, _takes_gain, _fp32_cm = None, False, False
 
-    def __new__(cls, n_fft=1920, num_mels=80, sampling_rate=24000, hop_size=480, win_size=1920, fmin=0, fmax=8000, device="cuda"):
+    def __init_subclass__(cls):
+        cls._cache = {}
+
+    @classmethod
+    def _cached(cls, device, *setting):
         dev = torch.device(device)
         if dev.type != "cuda":
-            raise MmxError("LogMel works on device memory only (no CPU fallback)")
+            raise MmxError(f"{cls.__name__} works on device memory only (no CPU fallback)")
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        key = (n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, dev)
-        self = cls._cache.get(key)
+        self = cls._cache.get((*setting, dev))
         if self is None:
-            self = super().__new__(cls)
-            self._build(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, dev)
-            cls._cache[key] = self
+            self = object.__new__(cls)
+            self._build(*setting, dev)
+            cls._cache[(*setting, dev)] = self
         return self
+
+    def _tables(self, fb, kp=None):
+        self.filterbank = fb                             # fp32, as the reference holds it
+        self.bin0, self.n_bins = nonzero_bins(fb)
+        self.basis = packed3(dft_basis(self.n_fft, self.bin0, self.n_bins, kp), self.dev)
+        self.filt = packed3(filter_table(fb, self.bin0, self.n_bins), self.dev)
+
+    def _run(self, wave, lens, gain, time_major, dtype, out):
+        if not wave.is_cuda:
+            raise MmxError(f"{self._entry} works on device memory only (no CPU fallback)")
+        wave = wave.to(torch.float32)
+        if wave.dim() == 1:
+            wave = wave[None]
+        if wave.stride(1) != 1:
+            wave = wave.contiguous()
+        B, L = wave.shape
+        h_lens = d_lens = None
+        if lens is not None:
+            lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
+            assert len(lens) == B
+            h_lens = (C.c_int32 * B)(*lens)
+            d_lens = torch.tensor(lens, dtype=torch.int32, device=wave.device)
+        T = max(1, max(self.frames(n) for n in (lens or [L])))       # a member without a frame: the entry point refuses it
+        if time_major:
+            if out is None:
+                out = torch.empty(B, T, self.n_mels, dtype=TORCH_DT[dtype], device=wave.device)
+            assert out.is_contiguous() and tuple(out.shape) == (B, T, self.n_mels) and out.dtype == TORCH_DT[dtype]
+            cm, tm = None, out
+            if self._fp32_cm and out.dtype != torch.float32:
+                cm = torch.empty(B, self.n_mels, T, device=wave.device)
+        else:
+            cm, tm = torch.empty(B, self.n_mels, T, device=wave.device), None
+        if gain is not None:
+            gain = gain.to(torch.float32).reshape(B).contiguous()
+        check(getattr(load(), self._entry)(_p(wave), i64(wave.stride(0) if B > 1 else L), L, B, *([_p(gain)] if self._takes_gain else []),
+                                           _p(d_lens), h_lens, _p(self.basis), _p(self.filt), self.n_fft, self.hop, self.bin0, self.n_bins,
+                                           self.n_mels, _p(cm), i64(T), _p(tm), T, dtype, stream()), self._entry)
+        return tm if time_major else cm
+
+
+class LogMel(_LogMelTables):
+    """The device tables of one mel setting and the launch of mmx_logmel."""
+
+    _entry, _takes_gain = "mmx_logmel", True
+
+    def __new__(cls, n_fft=1920, num_mels=80, sampling_rate=24000, hop_size=480, win_size=1920, fmin=0, fmax=8000, device="cuda"):
+        return cls._cached(device, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax)
 
     def _build(self, n_fft, num_mels, sr, hop, win, fmin, fmax, dev):
         if win != n_fft:
@@ -123,24 +210,7 @@ class LogMel:
             raise MmxError(f"mmx_logmel: unsupported setting n_fft {n_fft} hop {hop} n_mels {num_mels}")
         self.n_fft, self.hop, self.n_mels, self.dev = n_fft, hop, num_mels, dev
         self.pad = (n_fft - hop) // 2
-        self.filterbank = fb = mel_filterbank(sr, n_fft, num_mels, fmin, fmax)            # fp32, as the reference holds it
-        self.bin0, self.n_bins = nonzero_bins(fb)
-        nbp, mp = ops.round_up(self.n_bins, 32), ops.round_up(num_mels, 16)
-        # basis rows: bin i -> cos row 32 * (i // 16) + i % 16, sin row + 16 (a 16-row tile pair per 16 bins); float64, the phase
-        # reduced exactly in integers; periodic Hann window (torch.hann_window's default)
-        k = torch.arange(n_fft, dtype=torch.int64)
-        bins = torch.arange(self.bin0, self.bin0 + self.n_bins, dtype=torch.int64)
-        ang = ((bins[:, None] * k[None, :]) % n_fft).double() * (2 * math.pi / n_fft)
-        hann = 0.5 - 0.5 * torch.cos(k.double() * (2 * math.pi / n_fft))
-        i = torch.arange(self.n_bins)
-        rows = 32 * (i // 16) + i % 16
-        basis = torch.zeros(2 * nbp, n_fft, dtype=torch.float64)
-        basis[rows] = hann * torch.cos(ang)
-        basis[rows + 16] = hann * torch.sin(ang)
-        self.basis = torch.cat([ops.pack_skinny(p.to(dev).contiguous(), dtype=BF16) for p in _planes3(basis)])
-        filt = torch.zeros(mp, nbp, dtype=torch.float64)
-        filt[:num_mels, :self.n_bins] = torch.from_numpy(fb[:, self.bin0:self.bin0 + self.n_bins].astype(np.float64))
-        self.filt = torch.cat([ops.pack_skinny(p.to(dev).contiguous(), dtype=BF16) for p in _planes3(filt)])
+        self._tables(mel_filterbank(sr, n_fft, num_mels, fmin, fmax))
 
     def frames(self, n):
         return frames_of(n, self.n_fft, self.hop)
@@ -151,31 +221,4 @@ class LogMel:
         gain fp32 [B] on the device or None -> log-mel [B, n_mels, T] fp32 (the reference function's result), or with
         time_major=True [B, T, n_mels] in the activation type of `dtype` (written into `out` when given).  T = the frames of the
         longest member; a shorter member's remaining frames are 0."""
-        if not wave.is_cuda:
-            raise MmxError("mmx_logmel works on device memory only (no CPU fallback)")
-        wave = wave.to(torch.float32)
-        if wave.dim() == 1:
-            wave = wave[None]
-        if wave.stride(1) != 1:
-            wave = wave.contiguous()
-        B, L = wave.shape
-        h_lens = None
-        if lens is not None:
-            lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
-            assert len(lens) == B
-            h_lens = (C.c_int32 * B)(*lens)
-            d_lens = torch.tensor(lens, dtype=torch.int32, device=wave.device)
-        T = max(1, max(self.frames(n) for n in (lens or [L])))       # a member without a frame: the entry point refuses it
-        if gain is not None:
-            gain = gain.to(torch.float32).reshape(B).contiguous()
-        if time_major:
-            if out is None:
-                out = torch.empty(B, T, self.n_mels, dtype=TORCH_DT[dtype], device=wave.device)
-            assert out.is_contiguous() and tuple(out.shape) == (B, T, self.n_mels) and out.dtype == TORCH_DT[dtype]
-            cm, tm = None, out
-        else:
-            cm, tm = torch.empty(B, self.n_mels, T, device=wave.device), None
-        check(load().mmx_logmel(_p(wave), i64(wave.stride(0) if B > 1 else L), L, B, _p(gain), _p(d_lens) if lens is not None else None, h_lens,
-                                _p(self.basis), _p(self.filt), self.n_fft, self.hop, self.bin0, self.n_bins, self.n_mels,
-                                _p(cm), i64(T), _p(tm), T, dtype, stream()), "mmx_logmel")
-        return tm if time_major else cm
+        return self._run(wave, lens, gain, time_major, dtype, out)

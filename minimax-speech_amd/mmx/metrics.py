@@ -21,26 +21,25 @@ Waveform, from the seven sums of mmx_wave_sums (n samples, x the estimate, y the
     evaluated as |d0|^2 + 2 (1 - alpha) <d0, y0> + (1 - alpha)^2 |y0|^2 with d0 = x0 - y0, whose leading term is summed directly
     (no cancellation between |x0|^2 and |y0|^2 when the two signals are close).
 
-This module builds the tables (float64; the window folded into the DFT basis) and states the arithmetic around the launches.
+mmx/mel.py builds the tables (float64; the window folded into the DFT basis); this module states the arithmetic around the launches.
 There is no CPU fallback: a CPU tensor raises MmxError."""
 import ctypes as C
-import math
 
 import numpy as np
 import torch
 
+from . import mel as MEL
 from . import ops
-from ._lib import BF16, MmxError, check, i64, load, stream, _p
+from ._lib import MmxError, check, i64, load, stream, _p
 from .loudness import _batch
-from .mel import _planes3, mel_filterbank
 
 MEL_N_MELS = (5, 10, 20, 40, 80, 160, 320)               # dac-vae/loss.py:261-262
 MEL_WINDOWS = (32, 64, 128, 256, 512, 1024, 2048)
 STFT_WINDOWS = (2048, 512)                               # loss.py:176
 VALIDATION_STFT_WINDOWS = (1024, 2048)                   # what train.py's validation step builds its stft_loss with
-MAX_MELS = 384                                           # csrc/metrics.hip: 3 mel tiles per wave, 8 waves
+MAX_MELS = 384                                           # csrc/metrics.hip: SD_MT = 3 mel tiles per wave, 8 waves
 LDS_BYTES = 160 * 1024
-FRAMES_PER_TILE, SAMPLES_PER_CHUNK, GAP = 16, 4096, 16   # csrc/metrics.hip: frame tile, WS_CHUNK, SD_GAP
+FRAMES_PER_TILE, SAMPLES_PER_CHUNK, GAP = 16, 4096, 16   # csrc/spec_tile.h: frame tile, GAP as csrc/metrics.hip sets it; its WS_CHUNK
 
 
 def frames_of(n, n_fft):
@@ -53,8 +52,8 @@ def padded_bins(n_fft):
 
 
 def lds_bytes(n_fft, n_mels=0):
-    """Dynamic LDS of mmx_spec_dist's kernel (sd_lds of csrc/metrics.hip): sample planes of both signals (STFT mode) or of one signal
-    and its magnitude planes (mel mode), plus the reduction buffer."""
+    """Dynamic LDS of mmx_spec_dist's kernel (sd_lds of csrc/metrics.hip over spec_plane of csrc/spec_tile.h): sample planes of both
+    signals (STFT mode) or of one signal and its magnitude planes (mel mode), plus the reduction buffer."""
     hop = n_fft // 4
     span = 15 * hop + n_fft
     planes = 3 * 2 * (span + GAP * -(-span // hop))
@@ -76,33 +75,17 @@ def refusal(lens, n_fft, n_mels=0):
 
 
 def dft_basis(n_fft):
-    """float64 [2 * padded_bins, n_fft]: bin i -> row 32 * (i // 16) + i % 16 = hann[k] cos(2 pi i k / n_fft), that row + 16 the
-    sine (a 16-row tile pair per 16 bins); the phase reduced exactly in integers; periodic Hann window."""
-    n_bins, nbp = n_fft // 2 + 1, padded_bins(n_fft)
-    k = torch.arange(n_fft, dtype=torch.int64)
-    bins = torch.arange(n_bins, dtype=torch.int64)
-    ang = ((bins[:, None] * k[None, :]) % n_fft).double() * (2 * math.pi / n_fft)
-    hann = 0.5 - 0.5 * torch.cos(k.double() * (2 * math.pi / n_fft))
-    rows = 32 * (bins // 16) + bins % 16
-    basis = torch.zeros(2 * nbp, n_fft, dtype=torch.float64)
-    basis[rows] = hann * torch.cos(ang)
-    basis[rows + 16] = hann * torch.sin(ang)
-    return basis
+    """float64 [2 * padded_bins, n_fft]: mel.dft_basis over all n_fft // 2 + 1 bins."""
+    return MEL.dft_basis(n_fft, 0, n_fft // 2 + 1)
 
 
 def mel_table(rate, n_fft, n_mels, fmin=0.0, fmax=None):
     """float64 [n_mels rounded up to 16, padded_bins]: the fp32 filterbank the reference holds, zero padded."""
-    fb = mel_filterbank(rate, n_fft, n_mels, fmin, fmax)
-    filt = torch.zeros(ops.round_up(n_mels, 16), padded_bins(n_fft), dtype=torch.float64)
-    filt[:n_mels, :n_fft // 2 + 1] = torch.from_numpy(fb.astype(np.float64))
-    return filt
+    return MEL.filter_table(MEL.mel_filterbank(rate, n_fft, n_mels, fmin, fmax), 0, n_fft // 2 + 1)
 
 
 _tables = {}
-
-
-def _packed(m64, dev):
-    return torch.cat([ops.pack_skinny(p.to(dev).contiguous(), dtype=BF16) for p in _planes3(m64)])
+_packed = MEL.packed3
 
 
 def _device_tables(rate, n_fft, n_mels, fmin, fmax, dev):

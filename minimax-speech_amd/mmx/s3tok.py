@@ -3,21 +3,18 @@
 
 Reference: speech/tools/S3Tokenizer/s3tokenizer/model_v2.py (S3TokenizerV2: AudioEncoderV2, FSMNMultiHeadAttention, FSQCodebook),
 utils.py:220-267 (log_mel_spectrogram), :367-390 (merge_tokenized_segments); called from cli/frontend.py:92-102.  Three kernels
-are the tokenizer's own (csrc/s3tok.hip: mmx_logmel_w, mmx_s3_rope_fsmn, mmx_fsq_encode); the two stride-2 convolutions, the
+are the tokenizer's own (mmx_logmel_w of csrc/mel.hip; csrc/s3tok.hip: mmx_s3_rope_fsmn, mmx_fsq_encode); the two stride-2 convolutions, the
 LayerNorms, the fused Q | K | V projection (a zero bias segment for K), the out-projection, the MLP and the attention run on the
 entry points every other engine uses.  There is no CPU fallback: a CPU tensor raises MmxError.
 
 segment_plan and merge_segments are pure host functions (the > 30 s path of S3TokenizerV2._quantize_mixed_batch)."""
-import ctypes as C
-import math
 from typing import Dict, List
 
-import numpy as np
 import torch
 
 from . import mel as MEL
 from . import ops
-from ._lib import BF16, F32, X2, X2W, MmxError, TORCH_DT, check, i64, is_split, load, stream, _p
+from ._lib import BF16, F32, X2, X2W, MmxError, check, i64, is_split, load, stream, _p
 
 SAMPLE_RATE, N_FFT, HOP, N_MELS = 16000, 400, 160, 128
 MAX_FRAMES = 3000                                        # model_v2.py:401: more mel frames than this select the windowed path
@@ -76,77 +73,28 @@ def rope_tables():
 
 
 # ----------------------------------------------------------------------------- log-mel tables and launch
-class LogMelW:
+class LogMelW(MEL._LogMelTables):
     """The device tables of the Whisper-convention log-mel (utils.py:220-267: n_fft 400, hop 160, 128 mels at 16 kHz) and the
     launch of mmx_logmel_w.  The DFT basis has its K dimension zero padded from 400 to 416 columns."""
 
-    _cache = {}
+    _entry, _fp32_cm = "mmx_logmel_w", True              # the clip maximum is taken over fp32 values
 
     def __new__(cls, n_mels=N_MELS, device="cuda"):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise MmxError("LogMelW works on device memory only (no CPU fallback)")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self = cls._cache.get((n_mels, dev))
-        if self is None:
-            self = super().__new__(cls)
-            self._build(n_mels, dev)
-            cls._cache[(n_mels, dev)] = self
-        return self
+        return cls._cached(device, n_mels)
 
     def _build(self, n_mels, dev):
-        self.n_mels, self.dev = n_mels, dev
-        self.filterbank = fb = MEL.mel_filterbank(SAMPLE_RATE, N_FFT, n_mels)             # librosa.filters.mel's defaults
-        self.bin0, self.n_bins = MEL.nonzero_bins(fb)
-        kp, nbp, mp = ops.round_up(N_FFT, 32), ops.round_up(self.n_bins, 32), ops.round_up(n_mels, 16)
-        k = torch.arange(N_FFT, dtype=torch.int64)
-        bins = torch.arange(self.bin0, self.bin0 + self.n_bins, dtype=torch.int64)
-        ang = ((bins[:, None] * k[None, :]) % N_FFT).double() * (2 * math.pi / N_FFT)
-        hann = 0.5 - 0.5 * torch.cos(k.double() * (2 * math.pi / N_FFT))
-        i = torch.arange(self.n_bins)
-        rows = 32 * (i // 16) + i % 16
-        basis = torch.zeros(2 * nbp, kp, dtype=torch.float64)
-        basis[rows, :N_FFT] = hann * torch.cos(ang)
-        basis[rows + 16, :N_FFT] = hann * torch.sin(ang)
-        self.basis = torch.cat([ops.pack_skinny(p.to(dev).contiguous(), dtype=BF16) for p in MEL._planes3(basis)])
-        filt = torch.zeros(mp, nbp, dtype=torch.float64)
-        filt[:n_mels, :self.n_bins] = torch.from_numpy(fb[:, self.bin0:self.bin0 + self.n_bins].astype(np.float64))
-        self.filt = torch.cat([ops.pack_skinny(p.to(dev).contiguous(), dtype=BF16) for p in MEL._planes3(filt)])
+        self.n_fft, self.hop, self.n_mels, self.dev = N_FFT, HOP, n_mels, dev
+        self._tables(MEL.mel_filterbank(SAMPLE_RATE, N_FFT, n_mels), kp=ops.round_up(N_FFT, 32))    # librosa.filters.mel's defaults
+
+    def frames(self, n):
+        return frames_of(n)
 
     @torch.no_grad()
     def __call__(self, wave, lens=None, time_major=False, dtype=F32, out=None):
         """wave fp32 [B, L] (or [L]) on the device, zero padded where `lens` (a list of ints) gives fewer valid samples per member
         -> log-mel [B, n_mels, T] fp32 (the reference function's layout), or with time_major=True [B, T, n_mels] in the activation
         type of `dtype` (into `out` when given).  T = the frames of the longest member; a shorter member's remaining frames are 0."""
-        if not wave.is_cuda:
-            raise MmxError("mmx_logmel_w works on device memory only (no CPU fallback)")
-        wave = wave.to(torch.float32)
-        if wave.dim() == 1:
-            wave = wave[None]
-        if wave.stride(1) != 1:
-            wave = wave.contiguous()
-        B, L = wave.shape
-        h_lens = d_lens = None
-        if lens is not None:
-            lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
-            assert len(lens) == B
-            h_lens = (C.c_int32 * B)(*lens)
-            d_lens = torch.tensor(lens, dtype=torch.int32, device=wave.device)
-        T = max(1, max(frames_of(n) for n in (lens or [L])))
-        if time_major:
-            if out is None:
-                out = torch.empty(B, T, self.n_mels, dtype=TORCH_DT[dtype], device=wave.device)
-            assert out.is_contiguous() and tuple(out.shape) == (B, T, self.n_mels) and out.dtype == TORCH_DT[dtype]
-            cm, tm = None, out
-            if out.dtype != torch.float32:               # the clip maximum is taken over fp32 values
-                cm = torch.empty(B, self.n_mels, T, device=wave.device)
-        else:
-            cm, tm = torch.empty(B, self.n_mels, T, device=wave.device), None
-        check(load().mmx_logmel_w(_p(wave), i64(wave.stride(0) if B > 1 else L), L, B, _p(d_lens), h_lens, _p(self.basis), _p(self.filt),
-                                  N_FFT, HOP, self.bin0, self.n_bins, self.n_mels, _p(cm), i64(T), _p(tm), T, dtype, stream()),
-              "mmx_logmel_w")
-        return tm if time_major else cm
+        return self._run(wave, lens, None, time_major, dtype, out)
 
 
 # ----------------------------------------------------------------------------- the two other kernels

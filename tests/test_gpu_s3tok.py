@@ -1,5 +1,5 @@
-"""The S3 speech tokenizer on the device (csrc/s3tok.hip, mmx/s3tok.py) against float64: the three kernels on their own, then
-the engine by the token rule (tests/test_s3tok_host.py).
+"""The S3 speech tokenizer on the device (csrc/s3tok.hip, mmx_logmel_w of csrc/mel.hip, mmx/s3tok.py) against float64: the
+three kernels on their own, then the engine by the token rule (tests/test_s3tok_host.py).
 
 Outputs sit in sentinel-guarded buffers, inputs that must not be read hold NaN, and whatever lies outside the written window is
 compared bit for bit with a clone taken before the launch.  Every bound comes from the reference's own error, the number formats

@@ -95,3 +95,47 @@ def test_fixture_fp32_agrees_with_float64(gold, name, frames):
     assert np.abs(r32 - r64).max() <= tol
     w = gold["wave_" + name.split("_")[0]]
     assert w.dtype == np.float32 and abs(np.abs(w).max() - 1) < 1e-6
+
+
+@pytest.mark.parametrize("n", [32, 96])
+def test_metrics_basis_is_the_shared_builder(n):
+    from mmx import mel as M, metrics as MT
+    assert torch.equal(MT.dft_basis(n), M.dft_basis(n, 0, n // 2 + 1)) and torch.equal(MT.dft_basis(n), M.dft_basis(n))
+
+
+def test_basis_k_padding_is_exactly_zero():
+    from mmx import mel as M
+    plain, padded = M.dft_basis(48, 2, 20), M.dft_basis(48, 2, 20, kp=64)
+    assert plain.shape == (64, 48) and padded.shape == (64, 64) and padded.dtype == torch.float64
+    assert torch.equal(padded[:, :48], plain) and not padded[:, 48:].any() and plain.any()
+
+
+def test_basis_row_map_crosses_a_tile():
+    """n_bins 17: bin 16 opens the second 16-row tile pair (rows 32 and 48); rows of no bin are zero."""
+    from mmx import mel as M
+    n_fft, bin0, n_bins = 64, 3, 17
+    t = M.dft_basis(n_fft, bin0, n_bins)
+    assert t.shape == (64, n_fft)
+    k = np.arange(n_fft)
+    hann = 0.5 - 0.5 * np.cos(2 * np.pi * k / n_fft)
+    used = []
+    for i in range(n_bins):
+        row = 32 * (i // 16) + i % 16
+        used += [row, row + 16]
+        ph = 2 * np.pi * (((bin0 + i) * k) % n_fft) / n_fft
+        assert np.abs(t[row].numpy() - hann * np.cos(ph)).max() < 1e-15, i
+        assert np.abs(t[row + 16].numpy() - hann * np.sin(ph)).max() < 1e-15, i
+    assert used[-2:] == [32, 48]
+    assert not t[[r for r in range(64) if r not in used]].any()
+
+
+def test_planes3_sum_back_to_24_bits():
+    from mmx import mel as M
+    t = M.dft_basis(96)
+    p = M.planes3(t)
+    assert M._planes3 is M.planes3 and len(p) == 3 and all(q.dtype == torch.bfloat16 and q.shape == t.shape for q in p)
+    s = p[0].double() + p[1].double() + p[2].double()
+    assert ((s - t).abs() <= 2.0 ** -24 * t.abs()).all()
+    f = M.filter_table(M.mel_filterbank(16000, 96, 20), 1, 40)
+    assert f.shape == (32, 64) and f.dtype == torch.float64 and not f[20:].any() and not f[:, 40:].any()
+    assert torch.equal(torch.stack(M.planes3(f)).double().sum(0), f)      # fp32 values: three bf16 terms hold them exactly

@@ -28,7 +28,7 @@ GATED = [
     "est_resnet_kernel<unsigned short, 32, 4, 8, 2, false>", "est_resnet_kernel<unsigned short, 32, 4, 8, 2, true>",   # split build, 8 waves (cin = 256)
     "est_resnet_kernel<unsigned short, 32, 2, 4, 2, true>", "est_resnet_kernel<unsigned short, 32, 4, 4, 2, true>",
     "skinny3_kernel", "decode_attn_kernel", "sample_step_kernel", "attn_flash_kernel", "attn_flash_x_kernel", "attn_relpos",
-    "dac_ru_kernel", "gemm_win_kernel", "logmel_kernel", "pool_rows_kernel", "logmel_w_kernel", "logmel_w_finish", "s3_rope_fsmn_kernel",
+    "dac_ru_kernel", "gemm_win_kernel", "logmel_kernel", "pool_rows_kernel", "logmel_w_finish", "s3_rope_fsmn_kernel",
     "fsq_encode_kernel", "rownorm_kernel", "resample_sinc_kernel", "kweight_kernel", "kweight_carry_kernel", "loudness_gate_kernel",
     "scale_rows_kernel", "spec_dist_kernel", "spec_finish_kernel", "wave_sums_kernel", "wave_finish_kernel",
 ]
