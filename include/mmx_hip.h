@@ -689,6 +689,49 @@ int mmx_spec_dist(const float* x, int64_t x_bs, const float* y, int64_t y_bs, in
 int mmx_wave_sums(const float* x, int64_t x_bs, const float* y, int64_t y_bs, int L, int B, const int32_t* lens, float clip, double* work,
                   int cap, double* out, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Spectral-gate noise reduction (csrc/denoise.hip; the definitions are stated in mmx/denoise.py): the reference's SpectralGate
+ * (dac-vae/audiotools/ml/layers/spectral_gate.py, wrapped by transforms.NoiseReduce) on a ragged batch of mono rows, without a host
+ * sync, and with it an inverse STFT.  One scale n_fft (a multiple of 32, 32 .. 2048), hop = n_fft / 4, torch.stft(center=True) /
+ * torch.istft(center=True, length=len) with the square root of the periodic Hann window, frames(len) = 1 + len / hop,
+ * bins = n_fft / 2 + 1, nbp = bins rounded up to 32.
+ *   x      fp32 [B][x_bs >= L];  lens int32 [B] or NULL (= L), h_lens the same values in HOST memory (given exactly when lens is);
+ *          samples at or beyond lens[b] are never read.
+ *   basis  bf16 [3][2 * nbp][n_fft]: mmx_spec_dist's table with the sqrt-Hann window in place of the Hann window.
+ *
+ * mmx_gate_threshold: noise clips x -> thresh fp32 [B][t_bs >= bins]: per bin, mean + n_std * std (unbiased) over the clip's own
+ *   frames of dB = 20 log10 max(|N|, 1e-4).  dB, its sums and the finish are fp64 in a fixed order (per 32-frame tile into work, then
+ *   per clip in tile order); no atomics.   work f64 [B][cap][nbp][2], cap >= ceil(frames(L) / 32): scratch.
+ * mmx_gate_analyze: clips x and their thresholds (row b at thresh + b * t_bs; t_bs = 0 shares one row) ->
+ *   spec   fp32 [B][frames_cap][2 * nbp]: per frame the real parts of the nbp bins, then the imaginary parts (padded bins 0);
+ *   mask   uint8 [B][frames_cap][nbp]: 1 where 20 log10 max(|X|, 1e-4) < thresh (strict, fp64 comparison of the fp32 magnitude), 0 at
+ *          padded bins and at frames at or past frames(lens[b]); every byte is written.   frames_cap >= frames(L).
+ * mmx_gate_synthesize: spec and mask as written above -> out fp32 [B][o_bs >= L]:
+ *   gain = 1 - amount[b] * smooth(mask), smooth = conv2d with the normalised outer product of the triangles of 2 n_freq + 1 taps over
+ *   bins and 2 n_time + 1 taps over frames (n_freq, n_time <= 14), zero padded at the edges of the clip's OWN [bins, frames(lens[b])]
+ *   grid, evaluated exactly as an integer sum over (n_freq + 1)^2 (n_time + 1)^2;  spec * gain is inverted per frame as a product
+ *   against inv, multiplied by the window, overlap-added as a gather (each sample adds its <= 4 frames in ascending order; no
+ *   atomics), divided by the overlap-added window^2 and cropped by n_fft / 2.  Samples at or past lens[b] are written as 0.
+ *   inv    bf16 [3][n_fft][2 * nbp]: the inverse DFT as three planes, each in mmx_pack_skinny order: c_k cos(2 pi k s / n) / n at
+ *          [s][k] and -c_k sin(2 pi k s / n) / n at [s][nbp + k], c_k = 1 for k = 0 and n / 2 (whose imaginary entries are 0), 2
+ *          between, 0 at padded bins;
+ *   window fp32 [n_fft]: the synthesis window;   amount fp32 [B] on the device;
+ *   frames fp32 [B][frames_cap][n_fft]: scratch (the windowed frames).
+ *   The products run on the bf16 MFMA with both operands as three bf16 terms, fp32 accumulation; a workgroup takes 32 frames, whose
+ *   2 * nbp gated columns pass through the same LDS in chunks of at most 544, one after the other; a chunk's product starts from
+ *   zero in registers and is added, in chunk order, to what the earlier chunks left in `frames`, which is thus the accumulator
+ *   across chunks (each element read and written by the one thread that owns it), and the last chunk applies the window.
+ * A clip's threshold, mask and output depend on its own samples, length and arguments alone: solo and batched runs agree bit for bit.
+ * MMX_EARG, before anything is launched: n_fft < 32, > 2048 or not a multiple of 32; a clip (or L) with at most n_fft / 2 samples or
+ *   more than L; a capacity or stride below the stated one; n_freq or n_time outside [0, 14]. */
+int mmx_gate_threshold(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, const void* basis,
+                       int n_fft, double n_std, double* work, int cap, float* thresh, int64_t t_bs, hipStream_t stream);
+int mmx_gate_analyze(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, const void* basis, int n_fft,
+                     const float* thresh, int64_t t_bs, float* spec, uint8_t* mask, int frames_cap, hipStream_t stream);
+int mmx_gate_synthesize(const float* spec, const uint8_t* mask, int frames_cap, int L, int B, const int32_t* lens, const int32_t* h_lens,
+                        const void* inv, const float* window, int n_fft, int n_freq, int n_time, const float* amount, float* frames,
+                        float* out, int64_t o_bs, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

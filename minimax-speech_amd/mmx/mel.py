@@ -76,16 +76,19 @@ def planes3(v64):
 _planes3 = planes3
 
 
-def dft_basis(n_fft, bin0=0, n_bins=None, kp=None):
+def dft_basis(n_fft, bin0=0, n_bins=None, kp=None, window=None):
     """float64 [2 * (n_bins rounded up to 32), kp] for bins bin0 .. bin0 + n_bins - 1 (None: up to n_fft // 2): bin bin0 + i ->
     row 32 * (i // 16) + i % 16 = hann[k] cos(2 pi (bin0 + i) k / n_fft), that row + 16 the sine (a 16-row tile pair per 16 bins);
-    the phase reduced exactly in integers; periodic Hann window (torch.hann_window's default) folded in.  kp (None: n_fft) pads
-    the K dimension: columns at and beyond n_fft are zero."""
+    the phase reduced exactly in integers; periodic Hann window (torch.hann_window's default) folded in, or `window` [n_fft] (its
+    values taken as float64) in its place.  kp (None: n_fft) pads the K dimension: columns at and beyond n_fft are zero."""
     n_bins = n_fft // 2 + 1 - bin0 if n_bins is None else n_bins
     k = torch.arange(n_fft, dtype=torch.int64)
     bins = torch.arange(bin0, bin0 + n_bins, dtype=torch.int64)
     ang = ((bins[:, None] * k[None, :]) % n_fft).double() * (2 * math.pi / n_fft)
-    hann = 0.5 - 0.5 * torch.cos(k.double() * (2 * math.pi / n_fft))
+    if window is None:
+        hann = 0.5 - 0.5 * torch.cos(k.double() * (2 * math.pi / n_fft))
+    else:
+        hann = torch.as_tensor(window).double().reshape(n_fft)
     i = torch.arange(n_bins)
     rows = 32 * (i // 16) + i % 16
     basis = torch.zeros(2 * ops.round_up(n_bins, 32), n_fft if kp is None else kp, dtype=torch.float64)

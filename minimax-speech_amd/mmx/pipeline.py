@@ -179,6 +179,36 @@ class TtsEngine:
                 out[b] = w.reshape(wavs[b].shape)
         return out
 
+    def _gate(self, wavs, rates, denoise):
+        """Spectral-gate noise reduction of recordings before anything else sees them (mmx.denoise.spectral_gate, the reference's
+        NoiseReduce / SpectralGate).  wavs: a list of mono clips [n] on the device at `rates`; denoise: per clip None (the clip as it
+        is: nothing is launched) or a dict of spectral_gate's keywords, of which `noise` is required: a noise clip, or (start, stop)
+        in samples of the clip itself.  The clips that share a rate and a gate setting form one launch sequence; each is gated on its
+        own grid, so its result is that of its solo call, bit for bit.  No host sync."""
+        from .denoise import _is_span, spectral_gate
+        out, groups = list(wavs), {}
+        for i, d in enumerate(denoise):
+            if d is None:
+                continue
+            d = dict(d)
+            if "noise" not in d:
+                raise ValueError("denoise: the dict needs `noise` (a noise clip, or (start, stop) in samples of the clip itself)")
+            if d.pop("return_mask", False) or "lens" in d:
+                raise ValueError("denoise: return_mask and lens are not engine arguments")
+            nz, amount = d.pop("noise"), d.pop("denoise_amount", 1.0)
+            if _is_span(nz):
+                a, b = nz
+                if not 0 <= a < b <= wavs[i].numel():
+                    raise ValueError(f"denoise: the noise span ({a}, {b}) does not lie inside a clip of {wavs[i].numel()} samples")
+                nz = wavs[i][a:b]
+            groups.setdefault((int(rates[i]), tuple(sorted(d.items()))), []).append((i, nz.to(self.dev, torch.float32).reshape(-1), float(amount)))
+        for (_, setting), members in groups.items():
+            gated = spectral_gate([wavs[i] for i, _, _ in members], [nz for _, nz, _ in members],
+                                  denoise_amount=[a for _, _, a in members], **dict(setting))
+            for (i, _, _), w in zip(members, gated):
+                out[i] = w
+        return out
+
     @torch.no_grad()
     def token2wav(self, token: torch.Tensor, prompt_token: torch.Tensor, prompt_feat: torch.Tensor,
                   embedding: torch.Tensor, streaming=False, finalize=True, loudness_db=None) -> torch.Tensor:
@@ -260,7 +290,8 @@ class TtsEngine:
         return out
 
     @torch.no_grad()
-    def prompt_from_clip(self, wave, sample_rate, prompt_text=None, noise=None, generator=None, via_16k=True, normalize_db=None) -> dict:
+    def prompt_from_clip(self, wave, sample_rate, prompt_text=None, noise=None, generator=None, via_16k=True, normalize_db=None,
+                         denoise=None) -> dict:
         """prompt_from_audio from ONE recording (mono [n] / [1, n]) at any rate: the two resamplings happen here, on the device
         (mmx.resample.Resample).  via_16k=True is the reference's inference route: the file is brought to 16 kHz
         (utils/file_utils.py:44-50 load_wav) and the features are taken from THAT clip brought to 24 kHz (cli/frontend.py:157-162);
@@ -268,23 +299,31 @@ class TtsEngine:
         tools/extract_embedding.py:30).  A rate that is already the wanted one is not resampled.
         normalize_db: the clip is first brought to that integrated loudness at its own rate (LUFS, peak <= 1.0; _level, as
         DACVAE.compress normalises to -16 before it encodes, dac-vae/base.py:166-180), so tokens, latents and embedding all see the
-        same level-matched clip; None takes the clip at the level it has."""
+        same level-matched clip; None takes the clip at the level it has.
+        denoise: None (the clip as recorded: nothing is launched), or a dict of mmx.denoise.spectral_gate's keywords of which
+        `noise` is required (a noise clip, or (start, stop) in samples of this clip: the room tone before the speaker starts).  The
+        gate runs at the clip's own rate BEFORE the level matching, so the meter hears the cleaned speech."""
         from .resample import Resample
-        w = self._level(wave.to(self.dev, torch.float32).reshape(-1), normalize_db, int(sample_rate))
+        w = wave.to(self.dev, torch.float32).reshape(-1)
+        if denoise is not None:
+            w = self._gate([w], [int(sample_rate)], [denoise])[0]
+        w = self._level(w, normalize_db, int(sample_rate))
         w16 = Resample(sample_rate, 16000)(w)
         w24 = Resample(16000, SAMPLE_RATE)(w16) if via_16k else Resample(sample_rate, SAMPLE_RATE)(w)
         return self.prompt_from_audio(w16, w24, prompt_text, noise, generator)
 
     @torch.no_grad()
     def prompts_from_clips(self, waves, sample_rates, prompt_texts=None, noises=None, generator=None, via_16k=True,
-                           normalize_db=None) -> List[dict]:
+                           normalize_db=None, denoise=None) -> List[dict]:
         """prompt_from_clip for a list of recordings (mono [n] / [1, n]; sample_rates: one rate or one per clip) with the batched
         stages run once: the clips that share a rate go through ONE resample launch per target rate (mmx.resample.resample),
         all of them through ONE speech-tokenizer batch and ONE DAC-VAE encode (DacEncoderEngine.encode_ragged); the speaker
         embedding stays one reference_embedding per clip.  Entry i is the dict prompt_from_clip(waves[i], ...) returns, bit for
         bit where noises[i] [80, frames] is given (a `generator` instead gives one draw for the batch, each clip its own rows).
         normalize_db (one value, or one per clip with None entries): as prompt_from_clip, each clip metered alone at its own rate,
-        the clips that share a rate and a target in one launch sequence."""
+        the clips that share a rate and a target in one launch sequence.
+        denoise (one dict for all, or one per clip with None entries left alone): as prompt_from_clip, before the level matching;
+        the clips that share a rate and a gate setting in one launch sequence."""
         from .resample import resample as resample_clips
         n = len(waves)
         rates = [int(sample_rates)] * n if isinstance(sample_rates, (int, float)) else [int(r) for r in sample_rates]
@@ -295,6 +334,10 @@ class TtsEngine:
         ws = [w.to(self.dev, torch.float32).reshape(-1) for w in waves]
         if isinstance(normalize_db, (list, tuple)) and len(normalize_db) != n:
             raise ValueError("prompts_from_clips: normalize_db is one value or per clip")
+        if isinstance(denoise, (list, tuple)) and len(denoise) != n:
+            raise ValueError("prompts_from_clips: denoise is one dict or per clip")
+        if denoise is not None:
+            ws = self._gate(ws, rates, [_own(denoise, i) for i in range(n)])
         if normalize_db is not None:
             for r in sorted(set(rates)):
                 idx = [i for i in range(n) if rates[i] == r]

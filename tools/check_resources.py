@@ -31,6 +31,7 @@ GATED = [
     "dac_ru_kernel", "gemm_win_kernel", "logmel_kernel", "pool_rows_kernel", "logmel_w_finish", "s3_rope_fsmn_kernel",
     "fsq_encode_kernel", "rownorm_kernel", "resample_sinc_kernel", "kweight_kernel", "kweight_carry_kernel", "loudness_gate_kernel",
     "scale_rows_kernel", "spec_dist_kernel", "spec_finish_kernel", "wave_sums_kernel", "wave_finish_kernel",
+    "gate_stft_kernel", "gate_thresh_kernel", "gate_synth_kernel", "gate_ola_kernel",
 ]
 
 
