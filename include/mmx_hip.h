@@ -369,8 +369,18 @@ int mmx_swiglu(const float* gu, int64_t ldgu, int rows, int I, void* out, int64_
  * EOS (== eos_id) sets finished; ids > eos_id leave next_x unchanged (llm.py:755-756).
  * Every call advances state.step and state.pos (+1) of unfinished sequences.
  * forced != NULL: teacher forcing, forced[b*max_out + step] replaces the accepted token (the sampled id is
- * still recorded in sampled[b][step]).  logp_out (optional) receives log_softmax(logits).
- * error (field 7): 0 none; 1 = 100 EOS re-draws under ignore_eos still gave EOS (llm.py:271-273 raises there; the id is accepted);
+ * still recorded in sampled[b][step]).  logp_out (optional, fp32 [B][V], pitch V) receives log_softmax(logits).
+ * Shapes: any 0 < V <= 6656, any eos_id < V, any E > 0, any ldl >= V and ldx >= E are served; row b of the logits is
+ *   logits[b * ldl .. b * ldl + V), columns V..ldl of a row are never read (they may hold anything, NaN included).
+ * What a step writes, for an unfinished sequence b with valid logits and parameters: sampled[b][step] (if sampled != NULL),
+ *   logp_out[b][0..V) (if logp_out != NULL), words of state column b, and - on an accepted token only - out_tokens[b][n_out] and
+ *   next_x[b * ldx .. b * ldx + E).  No other word of any buffer is written: the rest of the rows, the words between E and ldx,
+ *   and every other sequence's rows keep their bits (tests/test_gpu_sampler_edges.py checks this contract).
+ * Candidates are the reference's for every valid distribution - exact ties are broken by index as its stable sort does, and a
+ *   row with more elements at or above the selection threshold than the kernel's candidate list holds is selected exactly too
+ *   (slower).  tau_r is taken as fp32: win_size * tau_r can differ from the reference's double product at an exact integer.
+ * error (field 7): 0 none; 1 = 100 EOS re-draws under ignore_eos still gave EOS (llm.py:271-273 raises there; the id is accepted:
+ *       sampled[b][step] = eos_id, finished = 1, step + 1, nothing appended);
  *   2 = the sequence's column of the sampler table is out of range (mmx_sample_step_tab only, see below);
  *   3 = the sequence's logits are not finite - a NaN, a +inf, or every one of them -inf, which is what an activation past the
  *       range of the fp16 planes (MMX_H2 above) turns into: state.finished = 1 for THAT sequence, nothing is drawn, its pos /

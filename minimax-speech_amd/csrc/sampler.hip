@@ -83,7 +83,9 @@ constexpr int SAMP_MAXK = 64;
 constexpr int SAMP_GROUPS = SAMP_THREADS / 8;   // 64 group maxima
 // candidates >= the top_k-th group maximum (ties / clustered values included).  With top_k = 64 the threshold is the SMALLEST group
 // maximum: covering all 64 groups takes ~300 of the largest elements on average and more than 512 in ~2 % of random inputs (coupon
-// collector), more than 2048 in ~1e-12
+// collector), more than 2048 in ~1e-12.  A row can still be built to exceed it (every large value inside fewer than top_k groups:
+// with top_k = 25, the 2496 ids of 24 groups above all others).  Past SAMP_LIST takers the list is not used at all: the top_k best
+// are selected exactly by top_k rounds of a block arg-max over the row (rolled, off the common path) - the same candidates, later.
 constexpr int SAMP_LIST = 2048;
 
 // (value, index) of the better of two candidates across lanes with a DPP control (see common.h dpp_f32)
@@ -252,7 +254,25 @@ __device__ __forceinline__ void sample_step_body(
             }
         }
         __syncthreads();
-        const int cnt = min(sh_cnt, SAMP_LIST);
+        const int cnt = sh_cnt;                            // takers, listed or not: the same in every thread
+        if (cnt > SAMP_LIST) {
+            // the list is incomplete (which takers it lacks depends on the order of the atomics), so ranks inside it mean
+            // nothing: select the top_k best of the whole row exactly instead - round r is a block arg-max over the elements
+            // that strictly follow round r-1's pick in the sort order.  p_lds is only read (the full-vocabulary draw still
+            // needs it), and every thread walks the elements it wrote itself.  cnt > SAMP_LIST >= top_k: no round runs dry.
+            ArgMax prev{INFINITY, -1};
+#pragma unroll 1
+            for (int r = 0; r < top_k; ++r) {
+                ArgMax a{-2.f, 0x7fffffff};
+#pragma unroll 1
+                for (int idx = tid; idx < V; idx += SAMP_THREADS) {
+                    const float v = p_lds[idx];
+                    if (precedes(prev.v, prev.i, v, idx)) a = better(a, ArgMax{v, idx});
+                }
+                prev = block_argmax(a, sha);
+                if (tid == 0) { cand_p[r] = prev.v; cand_i[r] = prev.i; }
+            }
+        } else
         // rank of list entry `id` inside the list: 8 lanes share the comparisons of one entry (64 entries per round)
         for (int id0 = 0; id0 < cnt; id0 += SAMP_THREADS / 8) {
             const int id = id0 + (tid >> 3), part = tid & 7;

@@ -203,7 +203,7 @@ def lm_inference(sd, cfg: QwenCfg, text, prompt_text, prompt_speech_token, seed:
 
 
 def decision_unstable(logp: torch.Tensor, decoded: List[int], noise_for_trial: Callable[[int], Callable], ignore_eos: bool, eos: int,
-                      tol: float = 6e-5, top_p=0.8, top_k=25) -> bool:
+                      tol: float = 6e-5, top_p=0.8, top_k=25, win_size=10, tau_r=0.1) -> bool:
     """Is the reference's draw at this step decided by a near-tie that a log-prob perturbation of `tol` can flip?  (Any two
     fp32 implementations of the LM differ by ~1e-5 in log-prob - the reference on another BLAS included - so over a long
     utterance such steps are where token ids can legitimately part.)  The reference's sampler (common.py:111-139) has three
@@ -212,7 +212,14 @@ def decision_unstable(logp: torch.Tensor, decoded: List[int], noise_for_trial: C
     argmax p_i / e_i (nucleus and, on repetition, full vocabulary).  Unstable = the sampled id changes when two adjacent
     sorted candidates closer than tol swap their values, or the running sum passes top_p within tol, or a race's two
     largest ratios are within 2 tol (relative)."""
-    base = sampling_ids_e(logp, decoded, noise_for_trial, ignore_eos, eos)
+    def draw(lp):                                         # sampling_ids_e around THIS sampler (it only knows the default one)
+        for trial in range(101):
+            top = ras_sampling_e(lp, decoded, noise_for_trial(trial), top_p, top_k, win_size, tau_r)
+            if (not ignore_eos) or top != eos:
+                break
+        return top
+
+    base = draw(logp)
     sv, si = logp.sort(descending=True, stable=True)
     p = logp.softmax(0)
     prob, idx = nucleus_candidates(logp, top_p, top_k)
@@ -224,7 +231,7 @@ def decision_unstable(logp: torch.Tensor, decoded: List[int], noise_for_trial: C
         if float(sv[i] - sv[i + 1]) < tol:
             q = logp.clone()
             q[si[i]], q[si[i + 1]] = logp[si[i + 1]], logp[si[i]]
-            if sampling_ids_e(q, decoded, noise_for_trial, ignore_eos, eos) != base:
+            if draw(q) != base:
                 return True
     trial = 0
     while True:                                           # the races of every trial the draw went through
@@ -233,9 +240,9 @@ def decision_unstable(logp: torch.Tensor, decoded: List[int], noise_for_trial: C
         if n > 1 and float((r.values[0] - r.values[1]) / r.values[0]) < 2 * tol:
             return True
         top = int(idx[r.indices[0]])
-        if sum(1 for t in decoded[-10:] if t == top) >= 1:
+        if sum(1 for t in decoded[-win_size:] if t == top) >= win_size * tau_r:
             rr = (p / noise(1, p.numel())).sort(descending=True)
-            if float((rr.values[0] - rr.values[1]) / rr.values[0]) < 2 * tol:
+            if p.numel() > 1 and float((rr.values[0] - rr.values[1]) / rr.values[0]) < 2 * tol:
                 return True
             top = int(rr.indices[0])
         if not ignore_eos or top != eos:
@@ -243,6 +250,59 @@ def decision_unstable(logp: torch.Tensor, decoded: List[int], noise_for_trial: C
         trial += 1
         if trial > 100:
             return True
+
+
+def draw_undecided(logp: torch.Tensor, decoded: List[int], noise_for_trial: Callable[[int], Callable], ignore_eos: bool, eos: int,
+                   mode=0, top_p=0.8, top_k=25, win_size=10, tau_r=0.1, gap=1e-3, cut=1e-4, race=1e-3) -> Optional[str]:
+    """None when the reference's draw (mode 0 ras_sampling, 1 nucleus_sampling, 2 random_sampling, inside the EOS re-draw loop)
+    is DECISIVE: no two fp32 softmaxes an ulp apart can yield different ids.  Otherwise the reason.  Stricter than
+    decision_unstable (no swap trials: a close pair is refused whether or not swapping it changes this draw):
+      order  adjacent candidates of the stable descending sort, up to and including the first excluded one, have exactly equal
+             log-probs (equal inputs stay equal through any softmax, so index order decides in every implementation) or log-probs
+             at least `gap` apart;
+      cut    while n < top_k the running sum stays `cut` away from top_p - unless every candidate from n on up to top_k has a
+             log-prob below -110: exp of it is 0 in fp32 (the smallest subnormal is e^-103.3), such candidates add nothing to the
+             sum and never win a race against a positive ratio, so the draw is the same on either side of that cut;
+      race   in every race that is run - the nucleus race of every trial, the full-vocabulary race where repetition or mode 2
+             asks for it - the two largest ratios p / e differ by at least `race` relative (one entry: no race)."""
+    p = logp.softmax(0)
+    V = p.numel()
+    if mode != 2:
+        sv, si = p.sort(descending=True, stable=True)
+        prob, idx = nucleus_candidates(logp, top_p, top_k)
+        n = prob.numel()
+        lp = logp[si[:n + 1]].double()
+        for i in range(min(n, V - 1)):
+            d = float(lp[i] - lp[i + 1])
+            if d != 0.0 and not d >= gap:
+                return f"order: sorted candidates {i} and {i + 1} are {d:.3g} apart in log-prob"
+        cum = torch.cumsum(sv[:min(top_k, V)], 0)
+        for m in range(1, min(top_k, V)):                 # the test `cum < top_p` with m candidates taken, more to take
+            if abs(float(cum[m - 1]) - top_p) < cut and not bool((logp[si[m:min(top_k, V)]] < -110.0).all()):
+                return f"cut: the running sum of {m} candidates is {float(cum[m - 1])!r}, top_p is {top_p}"
+
+    def close(r):
+        r = r.sort(descending=True).values
+        return r.numel() > 1 and not float((r[0] - r[1]) / r[0]) >= race
+
+    for trial in range(101):
+        noise = noise_for_trial(trial)
+        full = mode == 2
+        if mode != 2:
+            ratios = prob / noise(0, n)
+            if close(ratios):
+                return f"race: nucleus, trial {trial}"
+            top = int(idx[int(torch.argmax(ratios))])
+            if mode == 0:
+                full = sum(1 for t in decoded[-win_size:] if t == top) >= win_size * tau_r
+        if full:
+            ratios = p / noise(1, V)
+            if close(ratios):
+                return f"race: full vocabulary, trial {trial}"
+            top = int(torch.argmax(ratios))
+        if not ignore_eos or top != eos:
+            return None
+    return None                                           # 101 EOS draws: the reference raises, every race of them was clear
 
 
 def lm_inference_bistream(sd, cfg: QwenCfg, text_chunks, prompt_text, prompt_speech_token,

@@ -470,9 +470,11 @@ def test_decode_attn_one_token(env, dt, per_head, ctx):
 
 def test_sampler_matches_oracle(env):
     """Device sampler (log_softmax + RAS + EOS re-draw + bookkeeping) vs oracle.llm.sampling_ids_e on the same
-    Philox noise: ids must be IDENTICAL."""
+    Philox noise: ids must be IDENTICAL.  logp_out against float64 under the rule of test_gpu_sampler_table.py logp_error
+    (measured on MI355X: err / bound at most 0.199 over the 64 rows, errors 1.4e-7 .. 3.2e-6)."""
     from oracle import llm as OL
     from oracle import weights as W
+    from test_gpu_sampler_table import logp_error
     L, ops = env
     cases = W.sampler_cases(64)
     V, E, eos, seed = 6564, 896, 6561, 1234
@@ -495,7 +497,8 @@ def test_sampler_matches_oracle(env):
                         sampled=sampled, logp_out=lp)
         got = int(sampled[0, step])
         lpo = logits[0].log_softmax(-1)
-        assert (lp[0].cpu() - lpo).abs().max() < 1e-4
+        err, bound = logp_error(lp[0].cpu(), logits[0], f"case {s}")      # float64 rule of tests/test_gpu_sampler_edges.py; never above the old 1e-4
+        assert err <= min(bound, 1e-4), (s, err, bound)
         want = OL.sampling_ids_e(lpo, hist, lambda k: OL.philox_noise(seed, 3, step, k), ignore_eos=step < min_len, eos=eos)
         mism += got != want
         st = state.cpu().tolist()

@@ -43,8 +43,8 @@ def column(mode=0, top_p=0.8, top_k=25, win_size=10, tau_r=0.1, seed=0):
 class Seq:
     """One sequence of a sampler launch: its logits, history, loop state and sampler."""
 
-    def __init__(self, logits, hist, step, ignore_eos, seq, sampler, pos=40):
-        self.logits, self.hist, self.step, self.seq, self.pos = logits, list(hist), step, seq, pos
+    def __init__(self, logits, hist, step, ignore_eos, seq, sampler, pos=40, eos=EOS):
+        self.logits, self.hist, self.step, self.seq, self.pos, self.eos = logits, list(hist), step, seq, pos, eos
         self.min_len = step + 1 if ignore_eos else 0
         self.sp = dict(DEFAULT, seed=0)
         self.sp.update(sampler)
@@ -66,52 +66,110 @@ class Seq:
             else:
                 p = logp.softmax(dim=0)
                 top = OL.multinomial_e(p, noise(1, p.numel()))
-            if self.step >= self.min_len or top != EOS:
+            if self.step >= self.min_len or top != self.eos:
                 return top
         raise AssertionError("the oracle ran out of trials")
 
     def expected_state(self, top):
         st = self.state()
-        if top == EOS:
+        if top == self.eos:
             st[1], st[3] = self.step + 1, 1
         else:
             st[0], st[1] = self.pos + 1, self.step + 1
-            if top < EOS:
+            if top < self.eos:
                 st[2] = len(self.hist) + 1
         return st
 
 
-def buffers(seqs, V):
+GUARD = 256                                               # sentinel words on either side of every output buffer
+
+
+def guarded(shape, dtype, fill):
+    """(whole buffer, the view of `shape` in its middle): the style of tests/test_gpu_s3tok.py, with the launch's own fill."""
+    n = 1
+    for d in shape:
+        n *= d
+    buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device="cuda")
+    return buf, buf[GUARD:GUARD + n].view(*shape)
+
+
+def buffers(seqs, V, E=E, ldl=None, ldx=None, pad=float("nan"), logp=False):
+    """The launch's buffers.  Outputs sit between sentinel words; logits may have a pitch ldl > V (columns V..ldl hold `pad`),
+    next_x a pitch ldx > E; logp: a [B, V] logp_out buffer as well."""
     B = len(seqs)
-    logits = torch.stack([s.logits for s in seqs]).cuda().contiguous()
-    assert logits.shape == (B, V)
-    state = torch.tensor([s.state() for s in seqs], dtype=torch.int32).t().contiguous().cuda()
-    out_tokens = torch.full((B, MAX_OUT), -7, dtype=torch.int32)
+    ldl, ldx = ldl or V, ldx or E
+    logits = torch.full((B, ldl), pad)
+    logits[:, :V] = torch.stack([s.logits for s in seqs])
+    assert logits.shape == (B, ldl) and seqs[0].logits.numel() == V
+    raw = {}
+    raw["state"], state = guarded((8, B), torch.int32, -12345)
+    state.copy_(torch.tensor([s.state() for s in seqs], dtype=torch.int32).t())
+    raw["out_tokens"], out_tokens = guarded((B, MAX_OUT), torch.int32, -7)
     for b, s in enumerate(seqs):
-        out_tokens[b, :len(s.hist)] = torch.tensor(s.hist, dtype=torch.int32)
-    return dict(logits=logits, state=state, out_tokens=out_tokens.cuda(), sampled=torch.full((B, MAX_OUT), -1, dtype=torch.int32).cuda(),
-                next_x=torch.full((B, E), -3.0).cuda())
+        out_tokens[b, :len(s.hist)] = torch.tensor(s.hist, dtype=torch.int32).cuda()
+    raw["sampled"], sampled = guarded((B, MAX_OUT), torch.int32, -1)
+    raw["next_x"], next_x = guarded((B, ldx), torch.float32, -3.0)
+    bf = dict(logits=logits.cuda(), state=state, out_tokens=out_tokens, sampled=sampled, next_x=next_x, logp_out=None, raw=raw,
+              dims=(V, E))
+    if logp:
+        raw["logp_out"], bf["logp_out"] = guarded((B, V), torch.float32, -5.0)
+    bf["before"] = {k: v.clone() for k, v in raw.items()}
+    return bf
 
 
-def launch_tab(ops, emb, seqs, V, cols=None):
-    """One launch of the table entry point over `seqs` -> (sampled id, state column, out_tokens row, next_x row) per sequence."""
+def assert_only_named_words_written(bf, seqs):
+    """Every word of every output buffer, its sentinels included, holds the bits it held before the launch - except the words
+    include/mmx_hip.h says a step may write: sampled[b][step], out_tokens[b][n_out], next_x[b][:E], logp_out[b][:V] and the
+    sequence's 8 state words."""
+    V, E = bf["dims"]
+    for name, buf in bf["raw"].items():
+        may = torch.zeros(buf.numel(), dtype=torch.bool)
+        inner = may[GUARD:buf.numel() - GUARD].view(bf[name].shape)
+        for b, s in enumerate(seqs):
+            if name == "state":
+                inner[:, b] = True
+            elif name == "sampled":
+                inner[b, s.step] = True
+            elif name == "out_tokens":
+                inner[b, len(s.hist)] = True
+            elif name == "next_x":
+                inner[b, :E] = True
+            else:
+                inner[b, :V] = True
+        now, was = buf.cpu().view(torch.int32), bf["before"][name].cpu().view(torch.int32)
+        bad = (now != was) & ~may
+        assert not bool(bad.any()), (name, "written outside its words at", bad.nonzero().flatten()[:8].tolist())
+
+
+def rows_of(bf, seqs):
+    E_ = bf["dims"][1]
+    return [(int(bf["sampled"][b, s.step]), bf["state"][:, b].tolist(), bf["out_tokens"][b].cpu(), bf["next_x"][b, :E_].cpu())
+            for b, s in enumerate(seqs)]
+
+
+def launch_tab(ops, emb, seqs, V, cols=None, **kw):
+    """One launch of the table entry point over `seqs` -> (sampled id, state column, out_tokens row, next_x row) per sequence.
+    kw: the layout arguments of buffers()."""
     B = len(seqs)
-    bf = buffers(seqs, V)
+    bf = buffers(seqs, V, E=emb.shape[1], **kw)
     cols = [column(**s.sp) for s in seqs] if cols is None else cols
     samp = torch.tensor(cols, dtype=torch.int32).t().contiguous().cuda()
-    ops.sample_step_tab(bf["logits"], bf["state"], bf["out_tokens"], emb, bf["next_x"], samp, V=V, B=B, eos_id=EOS, sampled=bf["sampled"])
+    ops.sample_step_tab(bf["logits"], bf["state"], bf["out_tokens"], emb, bf["next_x"], samp, V=V, B=B, eos_id=seqs[0].eos,
+                        sampled=bf["sampled"], logp_out=bf["logp_out"])
     torch.cuda.synchronize()
-    return [(int(bf["sampled"][b, s.step]), bf["state"][:, b].tolist(), bf["out_tokens"][b].cpu(), bf["next_x"][b].cpu())
-            for b, s in enumerate(seqs)], bf
+    assert_only_named_words_written(bf, seqs)
+    return rows_of(bf, seqs), bf
 
 
-def launch_scalar(ops, emb, s, V):
-    bf = buffers([s], V)
+def launch_scalar(ops, emb, s, V, **kw):
+    bf = buffers([s], V, E=emb.shape[1], **kw)
     sp = s.sp
-    ops.sample_step(bf["logits"], bf["state"], bf["out_tokens"], emb, bf["next_x"], V=V, B=1, eos_id=EOS, seed=sp["seed"], top_k=sp["top_k"],
-                    top_p=sp["top_p"], win_size=sp["win_size"], tau_r=sp["tau_r"], sampled=bf["sampled"])
+    ops.sample_step(bf["logits"], bf["state"], bf["out_tokens"], emb, bf["next_x"], V=V, B=1, eos_id=s.eos, seed=sp["seed"],
+                    top_k=sp["top_k"], top_p=sp["top_p"], win_size=sp["win_size"], tau_r=sp["tau_r"], sampled=bf["sampled"],
+                    logp_out=bf["logp_out"])
     torch.cuda.synchronize()
-    return int(bf["sampled"][0, s.step]), bf["state"][:, 0].tolist(), bf["out_tokens"][0].cpu(), bf["next_x"][0].cpu()
+    assert_only_named_words_written(bf, [s])
+    return rows_of(bf, [s])[0]
 
 
 def check_against_oracle(s, got, emb, tag):
@@ -119,10 +177,23 @@ def check_against_oracle(s, got, emb, tag):
     want = s.oracle()
     assert top == want, (tag, top, want)
     assert st == s.expected_state(want), (tag, st)
-    if want < EOS:
+    if want < s.eos:
         assert int(out_row[len(s.hist)]) == want and torch.equal(nx, emb[want].cpu()), tag
     else:
         assert int(out_row[len(s.hist)]) == -7 and bool((nx == -3.0).all()), tag
+
+
+def logp_error(got, logits, tag=""):
+    """(max|got - f64|, its bound) of one logp_out row against float64 log_softmax of the same fp32 logits.  The bound is the rule of
+    the parity tests here, 4 * max(e_ref, 2^-23 * max|logp64|): e_ref is what torch's own fp32 log_softmax misses float64 by on this
+    row, the second term one fp32 rounding of the row's largest output (half an ulp of a value below 2^k is at most 2^-24 * 2^k
+    < 2^-23 |value|), which is the floor for any fp32 result.  Printed for the record."""
+    ref = logits.double().log_softmax(-1)
+    e_ref = float((logits.log_softmax(-1).double() - ref).abs().max())
+    bound = 4.0 * max(e_ref, 2.0 ** -23 * float(ref.abs().max()))
+    err = float((got.double() - ref).abs().max())
+    print(f"logp_out {tag}: err {err:.3e}  e_ref {e_ref:.3e}  bound {bound:.3e}  ratio {err / bound:.3f}")
+    return err, bound
 
 
 def widen(logits, V, s):
