@@ -742,6 +742,45 @@ int mmx_gate_synthesize(const float* spec, const uint8_t* mask, int frames_cap, 
                         const void* inv, const float* window, int n_fft, int n_freq, int n_time, const float* amount, float* frames,
                         float* out, int64_t o_bs, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Intelligibility (csrc/stoi.hip; the definition is stated in mmx/stoi.py): STOI and extended STOI between a reference and an
+ * estimate at 10 kHz, what the reference's audiotools.metrics.quality.stoi asks a host library for, on a ragged batch of mono rows
+ * of equal per-clip length, without a host sync and without atomics.  Frames of 256 samples at hop 128 that start strictly below
+ * len - 256: frames(len) = ceil((len - 256) / 128); a 512-point DFT of the windowed frame; 15 third-octave bands; segments of 30 frames.
+ *   est, ref fp32 [B][e_bs / r_bs >= L];  lens int32 [B] or NULL (= L), h_lens the same values in HOST memory (given exactly when
+ *            lens is); samples at or beyond lens[b] are never read.
+ *   window   fp32 [256]: numpy.hanning(258)[1:-1];   cap >= frames(L): the row count of every per-frame buffer below.
+ *
+ * mmx_stoi_select: the silent-frame decision, on the reference alone ->
+ *   energy f64 [B][cap]: 20 log10(|window * frame| + 2^-52) of the clip's frames(lens[b]) frames (fp32 products, fp64 sum in a fixed
+ *          order); entries past them are not written;
+ *   mask   uint8 [B][cap]: 1 where max(energy) - 40 - energy < 0, 0 elsewhere (every byte is written);
+ *   map    int32 [B][cap]: the source frame of kept frame i for i < F, in order (the exclusive scan of mask), -1 from F on;
+ *   kept   int32 [B]: F.
+ * mmx_stoi_bands: both signals rebuilt from their kept frames (each sample the sum of at most two windowed source samples found
+ *   through map: the overlap-add at hop 128 as a gather, never stored), the (F + 1) * 128 samples framed again into F - 1 frames,
+ *   their spectra on the bf16 MFMA (samples and |X|^2 as three bf16 terms, fp32 accumulation: mmx_spec_dist's arithmetic), ->
+ *   env    fp32 [B][2][cap][16]: sqrt of the band sums of |X|^2 per frame, signal 0 the reference, 1 the estimate, column 15 zero;
+ *          rows at and past F - 1 are not written.  F and map are read from device memory; no spectrogram is stored.
+ *   basis  bf16 [3][2 * 288][256]: mmx_spec_dist's table of n_fft = 512 with `window` followed by 256 zeros in place of the Hann
+ *          window, cut to its 256 non-zero columns;   filt bf16 [3][16][288]: the 0 / 1 band table, both in mmx_pack_skinny order.
+ * mmx_stoi_score: env and kept as written above -> out f64 [B]: the mean over the J = F - 30 segments (frames m - 30 .. m - 1 for
+ *   m = 30 .. F - 1) and the 15 bands of the correlation of the mean-removed, normalised segment of the reference with that of the
+ *   estimate scaled to the reference's norm and limited to (1 + 10^(15/20)) times the reference (extended = 0), or of the segments
+ *   normalised over rows, then over columns, summed and divided by 30 J (extended = 1); 1e-5 where F - 1 < 30.
+ *   frames int32 [B]: F - 1.   work f64 [B][wcap], wcap >= max(1, ceil((cap - 30) / 16)): scratch.
+ *   Every term is fp64, summed in a fixed order: per 16 segments into work, then per clip by the finishing launch.
+ * A clip's numbers depend on its own samples and length alone: solo and batched runs agree bit for bit.
+ * MMX_EARG, before anything is launched: a clip (or L) with at most 256 samples or more than L; lens without h_lens; a capacity or
+ *   stride below the stated one; extended outside {0, 1}. */
+int mmx_stoi_select(const float* ref, int64_t r_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, const float* window,
+                    double* energy, uint8_t* mask, int32_t* map, int32_t* kept, int cap, hipStream_t stream);
+int mmx_stoi_bands(const float* est, int64_t e_bs, const float* ref, int64_t r_bs, int L, int B, const int32_t* lens,
+                   const int32_t* h_lens, const float* window, const int32_t* map, const int32_t* kept, const void* basis,
+                   const void* filt, float* env, int cap, hipStream_t stream);
+int mmx_stoi_score(const float* env, int cap, int B, const int32_t* kept, int extended, double* work, int wcap, double* out,
+                   int32_t* frames, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

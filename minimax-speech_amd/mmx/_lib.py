@@ -38,6 +38,7 @@ SYMBOLS = [
     "mmx_est_tail", "mmx_est_resnet", "mmx_dac_ru", "mmx_pack_skinny", "mmx_skinny_gemm", "mmx_skinny2", "mmx_decode_prep", "mmx_rope_kv_store", "mmx_paged_attn", "mmx_decode_attn", "mmx_decode_attn_fin", "mmx_swiglu", "mmx_sample_step",
     "mmx_sample_step_tab", "mmx_logmel", "mmx_pool_rows", "mmx_logmel_w", "mmx_s3_rope_fsmn", "mmx_fsq_encode", "mmx_resample_sinc", "mmx_kweight_blocks", "mmx_loudness_gate", "mmx_scale_rows",
     "mmx_spec_dist", "mmx_wave_sums", "mmx_gate_threshold", "mmx_gate_analyze", "mmx_gate_synthesize",
+    "mmx_stoi_select", "mmx_stoi_bands", "mmx_stoi_score",
 ]
 
 

@@ -32,6 +32,7 @@ GATED = [
     "fsq_encode_kernel", "rownorm_kernel", "resample_sinc_kernel", "kweight_kernel", "kweight_carry_kernel", "loudness_gate_kernel",
     "scale_rows_kernel", "spec_dist_kernel", "spec_finish_kernel", "wave_sums_kernel", "wave_finish_kernel",
     "gate_stft_kernel", "gate_thresh_kernel", "gate_synth_kernel", "gate_ola_kernel",
+    "stoi_energy_kernel", "stoi_scan_kernel", "stoi_bands_kernel", "stoi_score_kernel", "stoi_finish_kernel",
 ]
 
 
