@@ -781,6 +781,44 @@ int mmx_stoi_bands(const float* est, int64_t e_bs, const float* ref, int64_t r_b
 int mmx_stoi_score(const float* env, int cap, int B, const int32_t* kept, int extended, double* work, int wcap, double* out,
                    int32_t* frames, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Room and noise simulation (csrc/degrade.hip; the definitions are stated in mmx/degrade.py): the reference's EffectMixin.convolve,
+ * apply_ir, alter_drr, measure_drr and mix (dac-vae/audiotools/core/effects.py:27-179, 540-647) on a ragged batch of mono fp32 rows,
+ * without a host sync.  Every `lens` array (int32 [B] in device memory, or NULL = the full width) comes with the same values in HOST
+ * memory (h_*; given exactly when the device array is); lengths lie in [1, width].
+ *
+ * mmx_ir_prepare: one impulse response per clip (ir fp32 [B][ir_bs >= Lir], or ir_bs = 0: one row shared by all), ir_lens / Lir its
+ *   lengths, sig_lens / Lsig the lengths of the clips it will be applied to ->
+ *   h_out fp32 [B][h_bs >= Lir]: the IR after alter_drr(drr[b]) (effects.py:617-647: early window of t0 = int(rate * 0.0025) samples
+ *         either side of the signed argmax, fp64 sums, the larger root, alpha floored at max|late| / max|early|, then
+ *         ensure_max_of_audio(1)); a NaN target, or drr = NULL, copies the IR.  A negative discriminant leaves NaNs, as the
+ *         reference does.  Columns from ir_lens[b] to Lir are zero.  h_out may not alias ir.
+ *   hann  f64 [2 t0 + 1][2 t0 + 1] (device): row c - 1 holds the periodic Hann window of c points.
+ *   taps  int32 [B]: L' = min(ir_lens[b], sig_lens[b]) (effects.py:85-90);  p int32 [B]: the first index of max |h_out[0 .. L')| when
+ *         start_at_max, else 0;  s fp32 [B]: 1 / max(max |h_out[0 .. L')|, 1e-5);  drr_out fp32 [B]: measure_drr of h_out,
+ *         10 log10(sum early^2 / sum late^2);
+ *   table bf16 [B][3][kcap / 32][64][8]: B[u][j] = g[u - j], g[v] = h_out[L' - 1 - v] (zero outside [0, L')), as three bf16 terms
+ *         in mmx_pack_skinny order; kcap a multiple of 32, at least max_b L' + 15 rounded up to 32.
+ * mmx_fir_rows: out[b][n] = s[b] * sum_{t < L'} h[t] X(n + p[b] - t) for n < lens[b], X(i) = x[b][i mod lens[b]] (wrap = 1) or x[b][i]
+ *   inside the clip and 0 outside (wrap = 0); zeros from lens[b] to L.  A six-term bf16 MFMA product (fp32 accumulation, K ascending)
+ *   of the clip's frames at hop 16 against `table`.  peak fp32 [B]: max |out[b]| (zeroed here, then an atomic max on the bit pattern).
+ *   An output's bits depend on its clip, its prepared IR and its position alone.  out may not alias x.
+ * mmx_row_absmax: peak fp32 [B] = max |x[b][0 .. lens[b])|, zeroed here.
+ * mmx_mix_rows: out[b][j] = x[b][j] + exp(((lx[b] - snr[b]) - ln[b]) ln 10 / 20) * noise[b][j] for j < lens[b] (noise reads as zero
+ *   from nlens[b] on), zeros from lens[b] to L;  lx, ln, snr fp32 [B] in device memory.
+ * MMX_EARG, before anything is launched or written: more than 65536 taps (max_b L'), a length outside [1, width], lens without h_lens,
+ *   a stride or capacity below the stated one, wrap outside {0, 1}. */
+int mmx_ir_prepare(const float* ir, int64_t ir_bs, int Lir, int B, const int32_t* ir_lens, const int32_t* h_ir_lens, int Lsig,
+                   const int32_t* sig_lens, const int32_t* h_sig_lens, const float* drr, int t0, const double* hann, int start_at_max,
+                   float* h_out, int64_t h_bs, int32_t* p, float* s, int32_t* taps, float* drr_out, void* table, int kcap,
+                   hipStream_t stream);
+int mmx_fir_rows(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, const void* table, int kcap,
+                 const int32_t* p, const float* s, const int32_t* taps, int wrap, float* out, int64_t o_bs, float* peak,
+                 hipStream_t stream);
+int mmx_row_absmax(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, float* peak, hipStream_t stream);
+int mmx_mix_rows(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const float* noise, int64_t n_bs, int Ln,
+                 const int32_t* nlens, const float* lx, const float* ln, const float* snr, float* out, int64_t o_bs, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

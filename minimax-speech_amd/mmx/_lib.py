@@ -39,6 +39,7 @@ SYMBOLS = [
     "mmx_sample_step_tab", "mmx_logmel", "mmx_pool_rows", "mmx_logmel_w", "mmx_s3_rope_fsmn", "mmx_fsq_encode", "mmx_resample_sinc", "mmx_kweight_blocks", "mmx_loudness_gate", "mmx_scale_rows",
     "mmx_spec_dist", "mmx_wave_sums", "mmx_gate_threshold", "mmx_gate_analyze", "mmx_gate_synthesize",
     "mmx_stoi_select", "mmx_stoi_bands", "mmx_stoi_score",
+    "mmx_ir_prepare", "mmx_fir_rows", "mmx_row_absmax", "mmx_mix_rows",
 ]
 
 

@@ -209,6 +209,38 @@ class TtsEngine:
                 out[i] = w
         return out
 
+    def _degrade(self, wavs, rates, degrade):
+        """Room and noise simulation of recordings before anything else sees them (mmx.degrade.apply_ir, then mmx.degrade.mix: the
+        reference's RoomImpulseResponse / BackgroundNoise transforms).  wavs: a list of mono clips [n] on the device at `rates`;
+        degrade: per clip None (the clip as it is: nothing is launched) or a dict with `ir` (an impulse response at the clip's rate;
+        optional `drr`, `wrap`, `start_at_max`) and / or `noise` with `snr` (default 10 dB).  The IR is applied first, then the noise.
+        The clips that share a rate and a setting form one launch sequence; each clip's result is that of its solo call, bit for
+        bit.  No host sync."""
+        from .degrade import apply_ir, mix
+        out, groups = list(wavs), {}
+        for i, d in enumerate(degrade):
+            if d is None:
+                continue
+            d = dict(d)
+            ir, nz = d.pop("ir", None), d.pop("noise", None)
+            drr, snr = d.pop("drr", None), d.pop("snr", 10.0)
+            wrap, at_max = bool(d.pop("wrap", True)), bool(d.pop("start_at_max", True))
+            if d or (ir is None and nz is None):
+                raise ValueError(f"degrade: a dict with `ir` (drr, wrap, start_at_max) and / or `noise` (snr); got also {sorted(d)}")
+            dev = lambda t: None if t is None else t.to(self.dev, torch.float32).reshape(-1)
+            groups.setdefault((int(rates[i]), ir is not None, nz is not None, wrap, at_max), []).append((i, dev(ir), drr, dev(nz), float(snr)))
+        for (rate, has_ir, has_noise, wrap, at_max), members in groups.items():
+            clips = [out[i] for i, *_ in members]
+            if has_ir:
+                drrs = [m[2] for m in members]
+                clips = apply_ir(clips, [m[1] for m in members], rate, drr=None if all(v is None for v in drrs) else drrs,
+                                 start_at_max=at_max, wrap=wrap)
+            if has_noise:
+                clips = mix(clips, [m[3] for m in members], rate, snr=[m[4] for m in members])
+            for (i, *_), w in zip(members, clips):
+                out[i] = w
+        return out
+
     @torch.no_grad()
     def token2wav(self, token: torch.Tensor, prompt_token: torch.Tensor, prompt_feat: torch.Tensor,
                   embedding: torch.Tensor, streaming=False, finalize=True, loudness_db=None) -> torch.Tensor:
@@ -291,7 +323,7 @@ class TtsEngine:
 
     @torch.no_grad()
     def prompt_from_clip(self, wave, sample_rate, prompt_text=None, noise=None, generator=None, via_16k=True, normalize_db=None,
-                         denoise=None) -> dict:
+                         denoise=None, degrade=None) -> dict:
         """prompt_from_audio from ONE recording (mono [n] / [1, n]) at any rate: the two resamplings happen here, on the device
         (mmx.resample.Resample).  via_16k=True is the reference's inference route: the file is brought to 16 kHz
         (utils/file_utils.py:44-50 load_wav) and the features are taken from THAT clip brought to 24 kHz (cli/frontend.py:157-162);
@@ -302,9 +334,14 @@ class TtsEngine:
         same level-matched clip; None takes the clip at the level it has.
         denoise: None (the clip as recorded: nothing is launched), or a dict of mmx.denoise.spectral_gate's keywords of which
         `noise` is required (a noise clip, or (start, stop) in samples of this clip: the room tone before the speaker starts).  The
-        gate runs at the clip's own rate BEFORE the level matching, so the meter hears the cleaned speech."""
+        gate runs at the clip's own rate BEFORE the level matching, so the meter hears the cleaned speech.
+        degrade: None (nothing is launched), or a dict with `ir` (plus optional `drr`, `wrap`, `start_at_max`) and / or `noise` plus
+        `snr`: the room and the noise of mmx.degrade (_degrade), at the clip's own rate, IR first and then noise, BEFORE denoise and
+        the level matching - so a degraded and then cleaned prompt is expressible."""
         from .resample import Resample
         w = wave.to(self.dev, torch.float32).reshape(-1)
+        if degrade is not None:
+            w = self._degrade([w], [int(sample_rate)], [degrade])[0]
         if denoise is not None:
             w = self._gate([w], [int(sample_rate)], [denoise])[0]
         w = self._level(w, normalize_db, int(sample_rate))
@@ -314,7 +351,7 @@ class TtsEngine:
 
     @torch.no_grad()
     def prompts_from_clips(self, waves, sample_rates, prompt_texts=None, noises=None, generator=None, via_16k=True,
-                           normalize_db=None, denoise=None) -> List[dict]:
+                           normalize_db=None, denoise=None, degrade=None) -> List[dict]:
         """prompt_from_clip for a list of recordings (mono [n] / [1, n]; sample_rates: one rate or one per clip) with the batched
         stages run once: the clips that share a rate go through ONE resample launch per target rate (mmx.resample.resample),
         all of them through ONE speech-tokenizer batch and ONE DAC-VAE encode (DacEncoderEngine.encode_ragged); the speaker
@@ -323,7 +360,9 @@ class TtsEngine:
         normalize_db (one value, or one per clip with None entries): as prompt_from_clip, each clip metered alone at its own rate,
         the clips that share a rate and a target in one launch sequence.
         denoise (one dict for all, or one per clip with None entries left alone): as prompt_from_clip, before the level matching;
-        the clips that share a rate and a gate setting in one launch sequence."""
+        the clips that share a rate and a gate setting in one launch sequence.
+        degrade (one dict for all, or one per clip with None entries left alone): as prompt_from_clip, before denoise; the clips that
+        share a rate and a setting in one launch sequence."""
         from .resample import resample as resample_clips
         n = len(waves)
         rates = [int(sample_rates)] * n if isinstance(sample_rates, (int, float)) else [int(r) for r in sample_rates]
@@ -336,6 +375,10 @@ class TtsEngine:
             raise ValueError("prompts_from_clips: normalize_db is one value or per clip")
         if isinstance(denoise, (list, tuple)) and len(denoise) != n:
             raise ValueError("prompts_from_clips: denoise is one dict or per clip")
+        if isinstance(degrade, (list, tuple)) and len(degrade) != n:
+            raise ValueError("prompts_from_clips: degrade is one dict or per clip")
+        if degrade is not None:
+            ws = self._degrade(ws, rates, [_own(degrade, i) for i in range(n)])
         if denoise is not None:
             ws = self._gate(ws, rates, [_own(denoise, i) for i in range(n)])
         if normalize_db is not None:

@@ -33,6 +33,7 @@ GATED = [
     "scale_rows_kernel", "spec_dist_kernel", "spec_finish_kernel", "wave_sums_kernel", "wave_finish_kernel",
     "gate_stft_kernel", "gate_thresh_kernel", "gate_synth_kernel", "gate_ola_kernel",
     "stoi_energy_kernel", "stoi_scan_kernel", "stoi_bands_kernel", "stoi_score_kernel", "stoi_finish_kernel",
+    "ir_prepare_kernel", "ir_table_kernel", "fir_rows_kernel", "row_absmax_kernel", "mix_rows_kernel",
 ]
 
 
