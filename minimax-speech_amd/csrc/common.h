@@ -65,6 +65,17 @@ inline int dispatch_dtype(int dtype, F&& f) {
 }
 inline int launch_status() { MMX_LAUNCH_CHECK(); return MMX_OK; }
 
+// A ragged batch [B][L]: row b holds lens[b] valid samples, every row whole where lens is NULL.
+// row_len: whatever lens holds in device memory, the length a kernel works with lies within [0, L].
+__device__ __forceinline__ int row_len(const int* __restrict__ lens, int b, int L) { return lens ? max(0, min(lens[b], L)) : L; }
+// rows_form: what the entry points refuse alike - lens comes with the same values in host memory (h_lens) or both are NULL, and
+// every length lies within [min_len, L].
+__forceinline__ int rows_form(int B, int L, const int32_t* lens, const int32_t* h_lens, int min_len) {
+    MMX_CHECK_ARG(B > 0 && B <= 65535 && L >= min_len && (!lens == !h_lens));
+    for (int b = 0; h_lens && b < B; ++b) MMX_CHECK_ARG(h_lens[b] >= min_len && h_lens[b] <= L);
+    return MMX_OK;
+}
+
 template <typename T> struct Cvt;
 template <> struct Cvt<float> {
     static __device__ __forceinline__ float to_f(float v) { return v; }

@@ -89,6 +89,14 @@ __device__ __forceinline__ int blk_argmax(const float* v, int n, float* kh, int*
     return ih[0] == 0x7fffffff ? 0 : ih[0];
 }
 
+// a wave's share of a row's max |x| (m its lanes' maxima, nan: a lane met a NaN) joins *peak by an atomic max on the bit pattern of
+// a non-negative float; NaN is the largest pattern: it stays
+__device__ __forceinline__ void peak_join(float m, bool nan, float* peak, int lane) {
+    m = wave_max(m);
+    if (__any(nan)) m = NAN;
+    if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(peak), __float_as_uint(fabsf(m)));
+}
+
 // hann: f64 [2 t0 + 1][2 t0 + 1], row c - 1 = the periodic Hann window of c points (scipy.signal.get_window("hann", c))
 __global__ __launch_bounds__(PREP_THREADS) void ir_prepare_kernel(const float* __restrict__ ir, long ir_bs, int Lir, const int* __restrict__ ir_lens,
                                                                 int Lsig, const int* __restrict__ sig_lens, const float* __restrict__ drr,
@@ -100,8 +108,8 @@ __global__ __launch_bounds__(PREP_THREADS) void ir_prepare_kernel(const float* _
     __shared__ float kh[PREP_THREADS];
     __shared__ int ih[PREP_THREADS];
     const int tid = threadIdx.x, b = blockIdx.x;
-    const int L = ir_lens ? max(1, min(ir_lens[b], Lir)) : Lir;
-    const int N = sig_lens ? max(1, min(sig_lens[b], Lsig)) : Lsig;
+    const int L = max(1, row_len(ir_lens, b, Lir));
+    const int N = max(1, row_len(sig_lens, b, Lsig));
     const float* src = ir + (long)b * ir_bs;
     float* dst = h_out + (long)b * h_bs;
     const int W = 2 * t0 + 1;
@@ -193,11 +201,7 @@ __global__ __launch_bounds__(256) void ir_table_kernel(const float* __restrict__
     const int e = idx & 7, lane = (idx >> 3) & 63, kt = (int)(idx >> 9);
     const int u = kt * 32 + (lane >> 4) * 8 + e, v = u - (lane & 15);
     const float val = (v >= 0 && v < taps) ? h[(long)b * h_bs + (taps - 1 - v)] : 0.f;
-    const Bf3 s = split3(val);
-    bf16_t* t = table + (long)b * 3 * PB + idx;
-    t[0] = s.h;
-    t[PB] = s.m;
-    t[2 * PB] = s.l;
+    put3(table + (long)b * 3 * PB, PB, idx, val);
 }
 
 __global__ __launch_bounds__(FIR_THREADS) void fir_rows_kernel(const float* __restrict__ x, long x_bs, int L, const int* __restrict__ lens,
@@ -209,7 +213,7 @@ __global__ __launch_bounds__(FIR_THREADS) void fir_rows_kernel(const float* __re
     const int g = lane >> 4, l16 = lane & 15;
     const int b = blockIdx.y;
     const long out0 = (long)blockIdx.x * FIR_NOUT;
-    const int N = lens ? max(0, min(lens[b], L)) : L;
+    const int N = row_len(lens, b, L);
     float* ob = out + (long)b * o_bs;
     const int width = (int)min((long)FIR_NOUT, L - out0);
     if (out0 >= N) {                                    // a workgroup of tail columns (uniform)
@@ -247,20 +251,14 @@ __global__ __launch_bounds__(FIR_THREADS) void fir_rows_kernel(const float* __re
             const long step = FIR_THREADS % N;
             long ii = i;
             for (int q = tid; q < fill; q += FIR_THREADS) {
-                const Bf3 s = split3(xb[ii]);
-                xs[q] = s.h;
-                xs[SP + q] = s.m;
-                xs[2 * SP + q] = s.l;
+                put3(xs, SP, q, xb[ii]);
                 ii += step;
                 if (ii >= N) ii -= N;
             }
         } else {
             for (int q = tid; q < fill; q += FIR_THREADS) {
                 const long i = first + q;
-                const Bf3 s = split3((i >= 0 && i < N) ? xb[i] : 0.f);
-                xs[q] = s.h;
-                xs[SP + q] = s.m;
-                xs[2 * SP + q] = s.l;
+                put3(xs, SP, q, (i >= 0 && i < N) ? xb[i] : 0.f);
             }
         }
         __syncthreads();
@@ -324,16 +322,14 @@ __global__ __launch_bounds__(FIR_THREADS) void fir_rows_kernel(const float* __re
             ob[out0 + n] = v;
         }
     }
-    float m = wave_max(pk);
-    if (__any(nan)) m = NAN;                            // NaN is the largest pattern: it stays
-    if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(peak + b), __float_as_uint(fabsf(m)));
+    peak_join(pk, nan, peak + b, lane);
 }
 
 constexpr int RM_THREADS = 256, RM_PER = 16;
 __global__ __launch_bounds__(RM_THREADS) void row_absmax_kernel(const float* __restrict__ x, long x_bs, int L, const int* __restrict__ lens,
                                                                float* __restrict__ peak) {
     const int b = blockIdx.y;
-    const int len = lens ? max(0, min(lens[b], L)) : L;
+    const int len = row_len(lens, b, L);
     const long j0 = (long)blockIdx.x * (RM_THREADS * RM_PER) + threadIdx.x;
     if ((long)blockIdx.x * (RM_THREADS * RM_PER) >= len) return;
     float m = 0.f;
@@ -347,9 +343,7 @@ __global__ __launch_bounds__(RM_THREADS) void row_absmax_kernel(const float* __r
             m = fmaxf(m, fabsf(v));
         }
     }
-    m = wave_max(m);
-    if (__any(nan)) m = NAN;
-    if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned*>(peak + b), __float_as_uint(fabsf(m)));
+    peak_join(m, nan, peak + b, threadIdx.x & 63);
 }
 
 __global__ __launch_bounds__(RM_THREADS) void mix_rows_kernel(const float* __restrict__ x, long x_bs, int L, const int* __restrict__ lens,
@@ -357,8 +351,8 @@ __global__ __launch_bounds__(RM_THREADS) void mix_rows_kernel(const float* __res
                                                              const float* __restrict__ lx, const float* __restrict__ ln,
                                                              const float* __restrict__ snr, float* __restrict__ out, long o_bs) {
     const int b = blockIdx.y;
-    const int len = lens ? max(0, min(lens[b], L)) : L;
-    const int nl = nlens ? max(0, min(nlens[b], Ln)) : Ln;
+    const int len = row_len(lens, b, L);
+    const int nl = row_len(nlens, b, Ln);
     // effects.py:60-61, 214-217: tgt = Lx - snr, gain = exp((tgt - Ln) ln 10 / 20); the differences in fp32 as torch takes them
     const float gain = (float)exp((double)((lx[b] - snr[b]) - ln[b]) * 0.11512925464970229);
     const long j0 = (long)blockIdx.x * (RM_THREADS * RM_PER) + threadIdx.x;
@@ -375,13 +369,6 @@ __global__ __launch_bounds__(RM_THREADS) void mix_rows_kernel(const float* __res
     }
 }
 
-// lens (device) come with the same values in host memory, or both are NULL; every length within [1, L]
-inline int rows_form(int B, int L, const int32_t* lens, const int32_t* h_lens) {
-    MMX_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && (!lens == !h_lens));
-    for (int b = 0; h_lens && b < B; ++b) MMX_CHECK_ARG(h_lens[b] >= 1 && h_lens[b] <= L);
-    return MMX_OK;
-}
-
 }  // namespace
 
 extern "C" int mmx_ir_prepare(const float* ir, int64_t ir_bs, int Lir, int B, const int32_t* ir_lens, const int32_t* h_ir_lens, int Lsig,
@@ -390,8 +377,8 @@ extern "C" int mmx_ir_prepare(const float* ir, int64_t ir_bs, int Lir, int B, co
                               void* table, int kcap, hipStream_t stream) {
     MMX_CHECK_ARG(ir && h_out && p && s && taps && drr_out && table && (const void*)ir != (const void*)h_out);
     MMX_CHECK_ARG((ir_bs == 0 || ir_bs >= Lir) && h_bs >= Lir && t0 >= 0 && t0 <= 4096 && hann);
-    if (int rc = rows_form(B, Lir, ir_lens, h_ir_lens)) return rc;
-    if (int rc = rows_form(B, Lsig, sig_lens, h_sig_lens)) return rc;
+    if (int rc = rows_form(B, Lir, ir_lens, h_ir_lens, 1)) return rc;
+    if (int rc = rows_form(B, Lsig, sig_lens, h_sig_lens, 1)) return rc;
     int most = 0;
     for (int b = 0; b < B; ++b) most = max(most, min(h_ir_lens ? h_ir_lens[b] : Lir, h_sig_lens ? h_sig_lens[b] : Lsig));
     MMX_CHECK_ARG(most <= FIR_MAX_TAPS && kcap > 0 && kcap % 32 == 0 && kcap >= fir_kp(most));
@@ -409,7 +396,7 @@ extern "C" int mmx_fir_rows(const float* x, int64_t x_bs, int L, int B, const in
                             float* peak, hipStream_t stream) {
     MMX_CHECK_ARG(x && table && p && s && taps && out && peak && x_bs >= L && o_bs >= L && (const void*)x != (const void*)out);
     MMX_CHECK_ARG(kcap >= 32 && kcap % 32 == 0 && kcap <= fir_kp(FIR_MAX_TAPS) && (wrap == 0 || wrap == 1));
-    if (int rc = rows_form(B, L, lens, h_lens)) return rc;
+    if (int rc = rows_form(B, L, lens, h_lens, 1)) return rc;
     if (hipMemsetAsync(peak, 0, sizeof(float) * B, stream) != hipSuccess) return MMX_EARG;
     const size_t lds = fir_lds(kcap);
     hipLaunchKernelGGL(fir_rows_kernel, dim3((L + FIR_NOUT - 1) / FIR_NOUT, B), dim3(FIR_THREADS), lds, stream, x, (long)x_bs, L, lens,

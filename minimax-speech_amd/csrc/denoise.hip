@@ -72,7 +72,7 @@ __global__ __launch_bounds__(GT_THREADS) void gate_stft_kernel(const float* __re
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int g = lane >> 4, l16 = lane & 15;
     const int b = blockIdx.y, t0 = blockIdx.x * GT_ROWS;
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     const int Tb = len > n / 2 ? gt_frames(len, hop) : 0;   // (the entry point refuses such a length)
     if (t0 >= Tb) {                                     // a tile of padding frames: no statistics; mask 0
         if constexpr (!STATS) {
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(64) void gate_thresh_kernel(const double* __restric
                                                         int n, int nbp, int nbins, double n_std, float* __restrict__ thresh, long t_bs) {
     const int k = blockIdx.x * 64 + threadIdx.x, b = blockIdx.y;
     if (k >= nbins) return;
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     const int T = gt_frames(max(len, 0), n / 4);
     const int tiles = min(cap, (T + GT_ROWS - 1) / GT_ROWS);
     double s1 = 0.0, s2 = 0.0;
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(GT_THREADS) void gate_synth_kernel(const float* __r
     bf16_t* mg = reinterpret_cast<bf16_t*>(smem + (size_t)GT_ROWS * nbp);             // [3][32][MS]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int b = blockIdx.y, t0 = blockIdx.x * GT_ROWS;
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     const int Tb = len > n / 2 ? gt_frames(len, hop) : 0;
     if (t0 >= Tb) return;                               // uniform over the workgroup
     const bool two = t0 + 16 < Tb;
@@ -281,11 +281,7 @@ __global__ __launch_bounds__(GT_THREADS) void gate_synth_kernel(const float* __r
                 const float gain = 1.f - amt * ((float)s / den);
                 v = sb[(long)t * 2 * nbp + q] * gain;
             }
-            const Bf3 v3 = split3(v);
-            bf16_t* d = mg + f * MS + c;
-            d[0] = v3.h;
-            d[GT_ROWS * MS] = v3.m;
-            d[2 * GT_ROWS * MS] = v3.l;
+            put3(mg + f * MS + c, GT_ROWS * MS, 0, v);
         }
         __syncthreads();
         // (c), (d) this chunk's inverse product into the frames workspace; the last chunk applies the synthesis window
@@ -303,7 +299,7 @@ __global__ __launch_bounds__(256) void gate_ola_kernel(const float* __restrict__
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j >= L) return;
     const int hop = n / 4;
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     float v = 0.f;
     if (j < len && len > n / 2) {
         const int Tb = gt_frames(len, hop);
@@ -324,11 +320,8 @@ __global__ __launch_bounds__(256) void gate_ola_kernel(const float* __restrict__
 
 // what the three entry points refuse alike; nbp out
 inline int gate_form(int n, int B, int L, const int32_t* lens, const int32_t* h_lens, int* nbp) {
-    MMX_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && n >= 32 && n % 32 == 0 && n <= GT_MAX_N && (!lens == !h_lens));
-    for (int b = 0; b < B; ++b) {
-        const int len = h_lens ? h_lens[b] : L;
-        MMX_CHECK_ARG(len > n / 2 && len <= L);         // the reflection reads sample n / 2
-    }
+    MMX_CHECK_ARG(n >= 32 && n % 32 == 0 && n <= GT_MAX_N);
+    if (int rc = rows_form(B, L, lens, h_lens, n / 2 + 1)) return rc;          // the reflection reads sample n / 2
     *nbp = (n / 2 + 1 + 31) / 32 * 32;
     MMX_CHECK_ARG(gt_stft_lds(n) <= 160 * 1024 && gt_synth_lds(*nbp) <= 160 * 1024);
     return MMX_OK;

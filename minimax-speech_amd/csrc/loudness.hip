@@ -79,7 +79,7 @@ __global__ __launch_bounds__(KW_THREADS) void kweight_kernel(const float* __rest
     __shared__ double sc[KW_THREADS][4];
     __shared__ double red[KW_THREADS];
     const int tid = threadIdx.x, b = blockIdx.y, i = blockIdx.x;            // i < cap
-    const int len = lens ? max(0, min(lens[b], L)) : L;
+    const int len = row_len(lens, b, L);
     const bool live = i < kw_nsub(len, rate, S, partial);
     const long s0 = (long)i * S;
     double* wk = work + ((long)b * cap + i) * 5;
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(64) void kweight_carry_kernel(int L, const int* __r
                                                           float* __restrict__ peak) {
     __shared__ double buf[64][4];
     const int lane = threadIdx.x, b = blockIdx.x;
-    const int len = lens ? max(0, min(lens[b], L)) : L;
+    const int len = row_len(lens, b, L);
     const int nsub = (int)min((long)cap, kw_nsub(len, rate, S, partial));
     double* wk = work + (long)b * cap * 5;
     const double* AS = tab + 10 + 16 * KW_STEPS;
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(64) void loudness_gate_kernel(const double* __restr
                                                           float max_peak, float* __restrict__ gain, unsigned char* __restrict__ mask,
                                                           long mask_bs) {
     const int lane = threadIdx.x, clip = blockIdx.x, row0 = clip * nch;
-    const int len = lens ? max(0, min(lens[row0], L)) : L;
+    const int len = row_len(lens, row0, L);
     const int F = (int)min((long)cap, kw_nsub(len, rate, S, partial)) - 3;
     const double den = 0.4 * (double)rate;
     const double* e = energy + (long)row0 * e_bs;
@@ -294,7 +294,7 @@ constexpr int SR_THREADS = 256, SR_PER = 4;
 __global__ __launch_bounds__(SR_THREADS) void scale_rows_kernel(const float* __restrict__ x, long x_bs, int L, const int* __restrict__ lens,
                                                                const float* __restrict__ gain, int nch, float* __restrict__ out, long o_bs) {
     const int b = blockIdx.y;
-    const int len = lens ? max(0, min(lens[b], L)) : L;
+    const int len = row_len(lens, b, L);
     const float g = gain[b / nch];
     const long j0 = (long)blockIdx.x * (SR_THREADS * SR_PER) + threadIdx.x;
 #pragma unroll

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(LM_WAVES * 64) void logmel_kernel(const float* __re
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int g = lane >> 4, l16 = lane & 15;
     const int b = blockIdx.y, t0 = blockIdx.x * 16;
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     const int Tb = Conv::frames(len, n_fft, hop);
 
     if (t0 >= Tb) {                                     // a tile of padding frames (uniform over the workgroup): zeros
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(LF_THREADS) void logmel_w_finish(const int* __restr
                                                               float* __restrict__ out_cm, long ldo, TO* __restrict__ out_tm, int T) {
     __shared__ float red[LF_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     const int Tb = min(Whisper::frames(len, n_fft, hop), T);
     const long n = (long)Tb * n_mels;
     if (n == 0) return;
@@ -144,11 +144,12 @@ int launch_logmel(const float* wave, int64_t w_bs, int L, int B, const float* ga
                   const void* basis, const void* filt, int n_fft, int hop, int n_bins, int n_mels, float* out_cm, int64_t ldo,
                   void* out_tm, int T, int act, hipStream_t stream) {
     const int pad = Conv::pad(n_fft, hop);
+    if (int rc = rows_form(B, L, lens, h_lens, pad + 1)) return rc;            // the reflection reads sample `pad`
     int tmax = 0;
     for (int b = 0; b < B; ++b) {
-        const int len = h_lens ? h_lens[b] : L;
-        MMX_CHECK_ARG(len > pad && len <= L && Conv::frames(len, n_fft, hop) > 0);   // the reflection reads sample `pad`
-        tmax = max(tmax, Conv::frames(len, n_fft, hop));
+        const int frames = Conv::frames(h_lens ? h_lens[b] : L, n_fft, hop);
+        MMX_CHECK_ARG(frames > 0);
+        tmax = max(tmax, frames);
     }
     MMX_CHECK_ARG(T >= tmax);                           // every frame a member has fits the outputs
     const int kp = Conv::kpad(n_fft), nbp = (n_bins + 31) / 32 * 32, mp = (n_mels + 15) / 16 * 16;
@@ -173,12 +174,11 @@ int launch_logmel(const float* wave, int64_t w_bs, int L, int B, const float* ga
 extern "C" int mmx_logmel(const float* wave, int64_t w_bs, int L, int B, const float* gain, const int32_t* lens,
                           const int32_t* h_lens, const void* basis, const void* filt, int n_fft, int hop, int bin0, int n_bins,
                           int n_mels, float* out_cm, int64_t ldo, void* out_tm, int T, int dtype, hipStream_t stream) {
-    MMX_CHECK_ARG(wave && basis && filt && (out_cm || out_tm) && B > 0 && B <= 65535 && T > 0 && L > 0);
+    MMX_CHECK_ARG(wave && basis && filt && (out_cm || out_tm) && T > 0);
     MMX_CHECK_ARG(n_fft > 0 && n_fft % 32 == 0 && n_mels > 0 && n_mels <= 128);
     MMX_CHECK_ARG(hop > 0 && hop <= n_fft && hop % 8 == 0 && (n_fft - hop) % 2 == 0);
     MMX_CHECK_ARG(bin0 >= 0 && n_bins > 0 && bin0 + n_bins <= n_fft / 2 + 1);
-    MMX_CHECK_ARG(w_bs >= L && (!out_cm || ldo >= T) && (!lens == !h_lens));
-    MMX_CHECK_ARG(L > Matcha::pad(n_fft, hop));         // the reflection reads sample `pad`
+    MMX_CHECK_ARG(w_bs >= L && (!out_cm || ldo >= T));
     return launch_logmel<Matcha>(wave, w_bs, L, B, gain, lens, h_lens, basis, filt, n_fft, hop, n_bins, n_mels, out_cm, ldo, out_tm, T,
                                  MMX_ACT_DTYPE(dtype), stream);
 }
@@ -186,11 +186,11 @@ extern "C" int mmx_logmel(const float* wave, int64_t w_bs, int L, int B, const f
 extern "C" int mmx_logmel_w(const float* wave, int64_t w_bs, int L, int B, const int32_t* lens, const int32_t* h_lens,
                             const void* basis, const void* filt, int n_fft, int hop, int bin0, int n_bins, int n_mels,
                             float* out_cm, int64_t ldo, void* out_tm, int T, int dtype, hipStream_t stream) {
-    MMX_CHECK_ARG(wave && basis && filt && (out_cm || out_tm) && B > 0 && B <= 65535 && T > 0 && L > 0);
+    MMX_CHECK_ARG(wave && basis && filt && (out_cm || out_tm) && T > 0);
     MMX_CHECK_ARG(n_fft > 0 && n_fft % 16 == 0 && n_mels > 0 && n_mels <= 128);
     MMX_CHECK_ARG(hop > 0 && hop <= n_fft && hop % 8 == 0);
     MMX_CHECK_ARG(bin0 >= 0 && n_bins > 0 && bin0 + n_bins <= n_fft / 2 + 1);
-    MMX_CHECK_ARG(w_bs >= L && (!out_cm || ldo >= T) && (!lens == !h_lens));
+    MMX_CHECK_ARG(w_bs >= L && (!out_cm || ldo >= T));
     const int act = MMX_ACT_DTYPE(dtype);
     MMX_CHECK_ARG(act == MMX_F32 || (act == MMX_BF16 && (out_cm || !out_tm)));   // the clip maximum is taken over fp32 values
     const int rc = launch_logmel<Whisper>(wave, w_bs, L, B, nullptr, lens, h_lens, basis, filt, n_fft, hop, n_bins, n_mels, out_cm, ldo,

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(SD_THREADS) void spec_dist_kernel(const float* __re
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int g = lane >> 4, l16 = lane & 15;
     const int b = blockIdx.y, t0 = blockIdx.x * 16;
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     const int Tb = sd_frames(len, hop);
     if (len <= n_fft / 2 || t0 >= Tb) return;           // (the entry point refuses such a length) / a tile of padding frames
     const long first = (long)t0 * hop - n_fft / 2;      // of the tile's span on the unpadded row
@@ -151,7 +151,7 @@ __device__ __forceinline__ void clip_sums(const double* __restrict__ w, int tile
 __global__ __launch_bounds__(64) void spec_finish_kernel(const double* __restrict__ work, int cap, const int* __restrict__ lens, int L,
                                                         int n_fft, int ncols, double pw, double* __restrict__ out) {
     const int lane = threadIdx.x, b = blockIdx.x, hop = n_fft / 4;
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     const int T = sd_frames(max(len, 0), hop);
     double s[2];
     clip_sums<2>(work + (long)b * cap * 2, min(cap, (T + 15) / 16), lane, s);
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(WS_THREADS) void wave_sums_kernel(const float* __re
                                                               int cap) {
     __shared__ double red[WS_THREADS / 64][7];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.y;
-    const int len = lens ? max(0, min(lens[b], L)) : L;
+    const int len = row_len(lens, b, L);
     const long j0 = (long)blockIdx.x * WS_CHUNK;
     if (j0 >= len) return;                              // uniform over the workgroup
     const float* xr = x + (long)b * x_bs;
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(WS_THREADS) void wave_sums_kernel(const float* __re
 __global__ __launch_bounds__(64) void wave_finish_kernel(const double* __restrict__ work, int cap, const int* __restrict__ lens, int L,
                                                         double* __restrict__ out) {
     const int lane = threadIdx.x, b = blockIdx.x;
-    const int len = lens ? max(0, min(lens[b], L)) : L;
+    const int len = row_len(lens, b, L);
     double s[7];
     clip_sums<7>(work + (long)b * cap * 7, (int)min((long)cap, ((long)len + WS_CHUNK - 1) / WS_CHUNK), lane, s);
     if (lane < 7) {
@@ -221,14 +221,11 @@ __global__ __launch_bounds__(64) void wave_finish_kernel(const double* __restric
 extern "C" int mmx_spec_dist(const float* x, int64_t x_bs, const float* y, int64_t y_bs, int L, int B, const int32_t* lens,
                              const int32_t* h_lens, const void* basis, const void* filt, int n_fft, int n_mels, double eps, double pow,
                              double* work, int cap, double* out, hipStream_t stream) {
-    MMX_CHECK_ARG(x && y && basis && work && out && B > 0 && B <= 65535 && L > 0 && x_bs >= L && y_bs >= L);
-    MMX_CHECK_ARG(n_fft >= 32 && n_fft % 32 == 0 && n_fft <= (1 << 20) && (!lens == !h_lens) && eps > 0.0);
+    MMX_CHECK_ARG(x && y && basis && work && out && x_bs >= L && y_bs >= L);
+    MMX_CHECK_ARG(n_fft >= 32 && n_fft % 32 == 0 && n_fft <= (1 << 20) && eps > 0.0);
     MMX_CHECK_ARG(n_mels >= 0 && n_mels <= 16 * SD_MT * SD_WAVES && (!n_mels == !filt));
     const int hop = n_fft / 4;
-    for (int b = 0; b < B; ++b) {
-        const int len = h_lens ? h_lens[b] : L;
-        MMX_CHECK_ARG(len > n_fft / 2 && len <= L);     // the reflection reads sample n_fft / 2
-    }
+    if (int rc = rows_form(B, L, lens, h_lens, n_fft / 2 + 1)) return rc;      // the reflection reads sample n_fft / 2
     MMX_CHECK_ARG(cap >= (sd_frames(L, hop) + 15) / 16);
     const int n_bins = n_fft / 2 + 1, nbp = (n_bins + 31) / 32 * 32, mp = (n_mels + 15) / 16 * 16;
     const size_t lds = sd_lds(n_fft, nbp, n_mels > 0);

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_sinc_kernel(const float* 
     float* xs = hs + cmax * n;                          // [span]
     const int tid = threadIdx.x, b = blockIdx.y;
     const int j0 = blockIdx.x * MMX_RESAMPLE_NOUT;      // < out_cols
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     const long olen = rs_out_len(len, o, n);
     float* y = out + (long)b * o_bs;
 
@@ -101,18 +101,15 @@ int rs_gcd(int a, int b) {
 extern "C" int mmx_resample_sinc(const float* wave, int64_t w_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, int orig,
                                  int neu, int width, const float* taps, const int32_t* first, const int32_t* count, int cmax,
                                  float* out, int64_t o_bs, int out_cols, hipStream_t stream) {
-    MMX_CHECK_ARG(wave && taps && first && count && out && B > 0 && B <= 65535 && L > 0 && out_cols > 0);
+    MMX_CHECK_ARG(wave && taps && first && count && out && out_cols > 0);
     MMX_CHECK_ARG(orig > 0 && neu > 0 && orig != neu && rs_gcd(orig, neu) == 1 && width > 0 && cmax > 0 && cmax <= 2 * width);
-    MMX_CHECK_ARG(w_bs >= L && o_bs >= out_cols && (!lens == !h_lens) && out_cols <= INT32_MAX - MMX_RESAMPLE_NOUT);
+    MMX_CHECK_ARG(w_bs >= L && o_bs >= out_cols && out_cols <= INT32_MAX - MMX_RESAMPLE_NOUT);
+    if (int rc = rows_form(B, L, lens, h_lens, 1)) return rc;
     // the layout's limit: the packed bank and one workgroup's input span share 64 KB of LDS
     const long bank = (long)cmax * neu, span = ((long)(MMX_RESAMPLE_NOUT - 1) * orig + neu - 1) / neu + 2L * width + 2;
     MMX_CHECK_ARG((bank + span) * (long)sizeof(float) <= (long)RS_LDS_MAX);
     long omax = 0;
-    for (int b = 0; b < B; ++b) {
-        const int len = h_lens ? h_lens[b] : L;
-        MMX_CHECK_ARG(len >= 1 && len <= L);
-        omax = max(omax, rs_out_len(len, orig, neu));
-    }
+    for (int b = 0; b < B; ++b) omax = max(omax, rs_out_len(h_lens ? h_lens[b] : L, orig, neu));
     MMX_CHECK_ARG(out_cols >= omax);                    // every output a clip has fits its row
     const size_t lds = (size_t)(bank + span) * sizeof(float);
     const dim3 grid((out_cols + MMX_RESAMPLE_NOUT - 1) / MMX_RESAMPLE_NOUT, B), block(RS_THREADS);

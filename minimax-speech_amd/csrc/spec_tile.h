@@ -3,6 +3,7 @@
 // v_mfma_f32_16x16x32_bf16 against three-plane float64-derived tables in mmx_pack_skinny order (mmx/mel.py builds them).
 //   spec_stage      stage 0: the sample span under the 16 frames (reflection as index arithmetic on the unpadded row) -> planes
 //   spec_dft_tile   stage 1: re / im of one 16-bin tile for one or two signals that share the basis fragments
+//   put3            a value -> its three bf16 terms in three planes
 //   spec_store3     a spectrum value -> the three magnitude planes
 //   spec_mel_tile   stage 2: one 16-mel tile of magnitudes x filter planes
 // GAP (compile time, 0 or 16): elements between hop-sized chunks of a sample plane.  The 16 frames of an A fragment start hop
@@ -25,6 +26,15 @@ __device__ __forceinline__ Bf3 split3(float v) {       // hi + mid + lo = v: the
     v -= bf2f(o.m);
     o.l = f2bf(v);
     return o;
+}
+
+// v as its three terms at position pos of three planes `stride` elements apart
+template <typename S, typename P>
+__device__ __forceinline__ void put3(bf16_t* planes, S stride, P pos, float v) {
+    const Bf3 s = split3(v);
+    planes[pos] = s.h;
+    planes[stride + pos] = s.m;
+    planes[2 * stride + pos] = s.l;
 }
 
 __device__ __forceinline__ short8_t ld8(const bf16_t* p) { return *reinterpret_cast<const short8_t*>(p); }
@@ -63,11 +73,7 @@ __device__ __forceinline__ void spec_stage(const float* __restrict__ x, int len,
         if (i >= len) i = 2L * (len - 1) - i;
         // beyond one reflection: only frames past the member's last reach there, and those enter no result
         const float v = (q < real && i >= 0 && i < len) ? __fmul_rn(x[i], gain) : 0.f;
-        const Bf3 s = split3(v);
-        const int p = spec_pos<GAP>(q, hop);
-        xs[p] = s.h;
-        xs[SP + p] = s.m;
-        xs[2 * SP + p] = s.l;
+        put3(xs, SP, spec_pos<GAP>(q, hop), v);
     }
 }
 
@@ -108,11 +114,7 @@ __device__ __forceinline__ void spec_dft_tile(const bf16_t* const (&xs)[NSIG], i
 
 // the spectrum value v of (frame, column col) -> mg[3][16][MS]; MS = columns + 8: 16-byte aligned rows, 4 banks apart
 __device__ __forceinline__ void spec_store3(bf16_t* mg, int MS, int frame, int col, float v) {
-    const Bf3 m3 = split3(v);
-    bf16_t* d = mg + frame * MS + col;
-    d[0] = m3.h;
-    d[16 * MS] = m3.m;
-    d[32 * MS] = m3.l;
+    put3(mg + frame * MS + col, 16 * MS, 0, v);         // the element's address first: the plane offsets stay wave-uniform
 }
 
 // stage 2: mels 16mt .. 16mt + 15 of the 16 frames in mg[3][16][MS]; the same C layout.  PF: elements per filter plane, nk2 = nbp / 32.

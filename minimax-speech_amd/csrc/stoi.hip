@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void stoi_energy_kernel(const float* __restric
                                                          const float* __restrict__ window, double* __restrict__ energy, int cap) {
     const int lane = threadIdx.x & 63, b = blockIdx.y;
     const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     if (f >= min(st_frames(len), cap)) return;          // uniform over the wave; 128 f + 255 < len - 1
     const float* r = ref + (long)b * r_bs + (long)f * ST_HOP;
     double s = 0.0;
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void stoi_scan_kernel(const double* __restrict
     __shared__ double wmax[4];
     __shared__ int wtot[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.x;
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     const int n = min(st_frames(len), cap);
     const double* e = energy + (long)b * cap;
     double m = -INFINITY;
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(ST_THREADS) void stoi_bands_kernel(const float* __r
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int g = lane >> 4, l16 = lane & 15;
     const int b = blockIdx.y, t0 = blockIdx.x * 16;
-    const int len = lens ? min(lens[b], L) : L;
+    const int len = row_len(lens, b, L);
     const int nf = min(st_frames(len), cap);            // source frames: a map entry is held below it, whatever the workspace holds
     const int F = min(max(kept[b], 0), nf);
     const int T = max(F - 1, 0);                        // frames of the (F + 1) * 128 samples that F kept frames rebuild
@@ -145,14 +145,9 @@ __global__ __launch_bounds__(ST_THREADS) void stoi_bands_kernel(const float* __r
             vx = __fadd_rn(vx, __fmul_rn(w, xr[s]));
             vy = __fadd_rn(vy, __fmul_rn(w, yr[s]));
         }
-        const Bf3 sx = split3(vx), sy = split3(vy);
         const int pos = spec_pos<ST_GAP>(q, ST_HOP);
-        xs[pos] = sx.h;
-        xs[ST_SP + pos] = sx.m;
-        xs[2 * ST_SP + pos] = sx.l;
-        xs[3 * ST_SP + pos] = sy.h;
-        xs[4 * ST_SP + pos] = sy.m;
-        xs[5 * ST_SP + pos] = sy.l;
+        put3(xs, ST_SP, pos, vx);
+        put3(xs + 3 * ST_SP, ST_SP, pos, vy);
     }
     __syncthreads();
 
@@ -307,11 +302,7 @@ __global__ __launch_bounds__(64) void stoi_finish_kernel(const double* __restric
 
 // what mmx_stoi_select and mmx_stoi_bands refuse alike
 inline int stoi_form(int L, int B, const int32_t* lens, const int32_t* h_lens, int cap) {
-    MMX_CHECK_ARG(B > 0 && B <= 65535 && L > ST_FRAME && (!lens == !h_lens));
-    for (int b = 0; b < B; ++b) {
-        const int len = h_lens ? h_lens[b] : L;
-        MMX_CHECK_ARG(len > ST_FRAME && len <= L);      // at least one frame
-    }
+    if (int rc = rows_form(B, L, lens, h_lens, ST_FRAME + 1)) return rc;       // at least one frame
     MMX_CHECK_ARG(cap >= st_frames(L));
     return MMX_OK;
 }

@@ -8,7 +8,7 @@ import torch
 from torch import nn
 
 import _mmx_path  # noqa: F401
-from mmx import metrics
+from mmx import clips, metrics
 
 
 def _audio(v):
@@ -59,7 +59,7 @@ class SISDRLoss(nn.Module):
     @torch.no_grad()
     def forward(self, x, y):
         (ref, _), (est, _) = _audio(x), _audio(y)
-        e, r, lens = metrics._pair(est, ref, None)
+        e, r, lens = clips.pack_pair(est, ref, None, "SISDRLoss")
         s = metrics.wave_sums(e, r, lens)
         sdr = -metrics.sisdr_from_sums(s, float(e.shape[1]), bool(self.scaling), bool(self.zero_mean))
         if self.clip_min is not None:

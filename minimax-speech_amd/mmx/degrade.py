@@ -27,15 +27,14 @@ looping a short noise clip (it is zero padded, as EffectMixin.mix itself does; t
 
 The one host table is the set of Hann windows (float64).  There is no CPU fallback: a CPU tensor raises MmxError before any device
 work."""
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
+from . import clips as CL
 from . import ops
 from ._lib import MmxError, check, i64, load, stream, _p
-from .loudness import _batch
 
 LDS_BYTES = 160 * 1024
 WAVES, ROW_TILES = 4, 4                                  # csrc/degrade.hip: FIR_WAVES, FIR_RT (a row tile: 16 frames x 16 columns)
@@ -181,67 +180,15 @@ def unpack_table(table):
 
 
 # ------------------------------------------------------------------------------------------------ launches
-def _clips(clips, lens, what):
-    """(fp32 [B, L] with unit stride along L, lens list) of a list of mono clips or a padded batch [B, L] / [B, 1, L] / [n]."""
-    if isinstance(clips, torch.Tensor):
-        if clips.dim() == 3 and clips.shape[1] == 1:
-            clips = clips[:, 0]
-        elif clips.dim() == 3:
-            raise ValueError(f"{what}: mono clips only, got {tuple(clips.shape)}")
-        items = [clips]
-    else:
-        clips = [w.reshape(-1) for w in clips]
-        items = clips
-        if not items:
-            raise ValueError(f"{what}: no clips")
-    if not all(w.is_cuda for w in items):
-        raise MmxError(f"{what} works on device memory only (no CPU fallback)")
-    if any(w.numel() == 0 for w in items):
-        raise MmxError(f"{what}: an empty clip")
-    x, lens = _batch(clips, lens)
-    return x, (lens if lens is not None else [x.shape[1]] * x.shape[0])
-
-
-def _lens_args(lens, width, dev):
-    """(device int32, host int32 array) of a list of lengths, or (None, None) where every row has the full width."""
-    if all(v == width for v in lens):
-        return None, None
-    return torch.tensor(lens, dtype=torch.int32, device=dev), (C.c_int32 * len(lens))(*lens)
-
-
-def _bs(t):
-    return i64(t.stride(0) if t.shape[0] > 1 else t.shape[1])
-
-
-def _per_clip(v, B, what, none=None):
-    """One value or one per clip -> a list of B floats (None entries -> `none`)."""
-    if isinstance(v, torch.Tensor):
-        if v.is_cuda:
-            raise ValueError(f"{what}: pass host values (a float or a list), not a device tensor")
-        v = v.reshape(-1).tolist()
-    vals = list(v) if isinstance(v, (list, tuple)) else [v] * B
-    if len(vals) != B:
-        raise ValueError(f"{what} is one value or one per clip ({B})")
-    return [none if e is None else float(e) for e in vals]
-
-
-_tables = {}
-
-
 def _hann(t0, dev):
-    key = (int(t0), str(dev))
-    if key not in _tables:
-        _tables[key] = torch.from_numpy(hann_windows(t0)).to(dev)
-    return _tables[key]
+    return CL.device_tables(("degrade", int(t0), str(dev)), lambda: torch.from_numpy(hann_windows(t0)).to(dev))
 
 
 def _prepare(irs, ir_lens, sig_lens, rate, drr, start_at_max, what):
     """irs: one IR [n], a list (one, or one per clip) or a padded batch [B, Lir] with ir_lens; sig_lens: the clips' lengths ->
     dict(ir fp32 [B, Lir], p, s, taps, drr, table, kcap), everything on the device."""
     B = len(sig_lens)
-    if isinstance(irs, torch.Tensor) and irs.dim() == 1:
-        irs = [irs]
-    h, hl = _clips(irs, ir_lens, f"{what} (impulse response)")
+    h, hl = CL.pack(irs, ir_lens, f"{what} (impulse response)")
     why = refusal(sig_lens, hl)
     if why:
         raise MmxError(f"{what}: {why}")
@@ -252,16 +199,16 @@ def _prepare(irs, ir_lens, sig_lens, rate, drr, start_at_max, what):
     t0 = int(rate * 0.0025) if rate is not None else 0
     d_drr = None
     if drr is not None:
-        vals = _per_clip(drr, B, f"{what}: drr", none=float("nan"))
+        vals = CL.per_clip(drr, B, f"{what}: drr", none=float("nan"))
         if any(v == v for v in vals):
             d_drr = torch.tensor(vals, dtype=torch.float32, device=dev)
-    d_il, h_il = _lens_args(hl, Lir, dev)
-    d_sl, h_sl = _lens_args(sig_lens, Lsig, dev)
+    d_il, h_il = CL.lens_args(hl, Lir, dev)
+    d_sl, h_sl = CL.lens_args(sig_lens, Lsig, dev)
     r = dict(ir=torch.empty(B, Lir, dtype=torch.float32, device=dev), p=torch.empty(B, dtype=torch.int32, device=dev),
              s=torch.empty(B, dtype=torch.float32, device=dev), taps=torch.empty(B, dtype=torch.int32, device=dev),
              drr=torch.empty(B, dtype=torch.float32, device=dev), table=torch.empty(B, 3, kcap * 16, dtype=torch.bfloat16, device=dev),
              kcap=kcap, ir_lens=hl)
-    check(load().mmx_ir_prepare(_p(h), i64(0) if shared else _bs(h), Lir, B, _p(d_il), h_il, Lsig, _p(d_sl), h_sl, _p(d_drr), t0,
+    check(load().mmx_ir_prepare(_p(h), i64(0) if shared else CL.row_stride(h), Lir, B, _p(d_il), h_il, Lsig, _p(d_sl), h_sl, _p(d_drr), t0,
                                 _p(_hann(t0, dev)), int(bool(start_at_max)), _p(r["ir"]), i64(Lir), _p(r["p"]), _p(r["s"]),
                                 _p(r["taps"]), _p(r["drr"]), _p(r["table"]), kcap, stream()), "mmx_ir_prepare")
     return r
@@ -270,29 +217,22 @@ def _prepare(irs, ir_lens, sig_lens, rate, drr, start_at_max, what):
 def _fir(x, lens, prep, wrap):
     """x fp32 [B, L] -> (out fp32 [B, L], zero past lens; peak fp32 [B] = max |out|)."""
     B, L = x.shape
-    d_lens, h_lens = _lens_args(lens, L, x.device)
+    d_lens, h_lens = CL.lens_args(lens, L, x.device)
     out = torch.empty(B, L, dtype=torch.float32, device=x.device)
     peak = torch.empty(B, dtype=torch.float32, device=x.device)
-    check(load().mmx_fir_rows(_p(x), _bs(x), L, B, _p(d_lens), h_lens, _p(prep["table"]), prep["kcap"], _p(prep["p"]), _p(prep["s"]),
+    check(load().mmx_fir_rows(_p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(prep["table"]), prep["kcap"], _p(prep["p"]), _p(prep["s"]),
                               _p(prep["taps"]), int(bool(wrap)), _p(out), i64(L), _p(peak), stream()), "mmx_fir_rows")
     return out, peak
 
 
 def row_absmax(x, lens=None):
     """max |x[b, :lens[b]]| of fp32 rows [B, L] on the device -> fp32 [B] (mmx_row_absmax)."""
-    if not x.is_cuda:
-        raise MmxError("row_absmax works on device memory only (no CPU fallback)")
+    CL.on_device("row_absmax", x)
     B, L = x.shape
-    d_lens = None if lens is None else torch.tensor([int(v) for v in lens], dtype=torch.int32, device=x.device)
+    d_lens, _ = CL.lens_args(lens, L, x.device)
     peak = torch.empty(B, dtype=torch.float32, device=x.device)
-    check(load().mmx_row_absmax(_p(x), _bs(x), L, B, _p(d_lens), _p(peak), stream()), "mmx_row_absmax")
+    check(load().mmx_row_absmax(_p(x), CL.row_stride(x), L, B, _p(d_lens), _p(peak), stream()), "mmx_row_absmax")
     return peak
-
-
-def _result(out, lens, as_list, shape):
-    if as_list:
-        return [out[b, :v] for b, v in enumerate(lens)]
-    return out.reshape(shape if len(shape) > 1 else (out.shape[1],))
 
 
 @torch.no_grad()
@@ -303,49 +243,45 @@ def convolve(clips, irs, lens=None, ir_lens=None, start_at_max=True, wrap=True):
     Returns the convolved clips: a list of [n] views for a list, a tensor of the input's shape (zero past `lens`) for a tensor.
     MmxError where refusal() gives a reason, or for a CPU tensor: nothing is launched then.  Nothing is read back; a clip's result
     is that of its solo call, bit for bit."""
-    as_list = not isinstance(clips, torch.Tensor)
-    shape = None if as_list else tuple(clips.shape)
-    x, lens = _clips(clips, lens, "convolve")
+    CL.on_device("convolve", clips, irs)
+    x, lens = CL.pack(clips, lens, "convolve")
     prep = _prepare(irs, ir_lens, lens, None, None, start_at_max, "convolve")
-    return _result(_fir(x, lens, prep, wrap)[0], lens, as_list, shape)
+    return CL.unpack(_fir(x, lens, prep, wrap)[0], lens, clips)
 
 
 @torch.no_grad()
 def apply_ir(clips, irs, rate, drr=None, start_at_max=True, wrap=True, lens=None, ir_lens=None):
     """EffectMixin.apply_ir for a ragged batch: alter_drr where `drr` (one value, or one per clip with None entries) names a target,
     convolve, then the rescale to the input's peak (effects.py:160-177, clamps of 1e-8).  Arguments and result as convolve."""
-    as_list = not isinstance(clips, torch.Tensor)
-    shape = None if as_list else tuple(clips.shape)
-    x, lens = _clips(clips, lens, "apply_ir")
+    CL.on_device("apply_ir", clips, irs)
+    x, lens = CL.pack(clips, lens, "apply_ir")
     prep = _prepare(irs, ir_lens, lens, rate, drr, start_at_max, "apply_ir")
     B, L = x.shape
-    d_lens = None if all(v == L for v in lens) else torch.tensor(lens, dtype=torch.int32, device=x.device)
-    before = torch.empty(B, dtype=torch.float32, device=x.device)
-    lib = load()
-    check(lib.mmx_row_absmax(_p(x), _bs(x), L, B, _p(d_lens), _p(before), stream()), "mmx_row_absmax")
+    d_lens, _ = CL.lens_args(lens, L, x.device)
+    before = row_absmax(x, lens)
     y, after = _fir(x, lens, prep, wrap)
     gain = before.clamp(min=1e-8) / after.clamp(min=1e-8)
     out = torch.zeros(B, L, dtype=torch.float32, device=x.device) if d_lens is not None else torch.empty_like(y)
-    check(lib.mmx_scale_rows(_p(y), i64(L), L, B, _p(d_lens), _p(gain), 1, _p(out), i64(L), stream()), "mmx_scale_rows")
-    return _result(out, lens, as_list, shape)
+    check(load().mmx_scale_rows(_p(y), i64(L), L, B, _p(d_lens), _p(gain), 1, _p(out), i64(L), stream()), "mmx_scale_rows")
+    return CL.unpack(out, lens, clips)
 
 
 @torch.no_grad()
 def alter_drr(irs, rate, drr, ir_lens=None):
     """EffectMixin.alter_drr for a ragged batch of impulse responses (a list, one IR, or [B, Lir] with `ir_lens`): drr is one target
     in dB or one per IR (None entries copy the IR) -> the altered IRs, a list of [n] views or a tensor of the input's shape."""
-    as_list = not isinstance(irs, torch.Tensor)
-    shape = None if as_list else tuple(irs.shape)
-    h, hl = _clips(irs, ir_lens, "alter_drr")
+    CL.on_device("alter_drr", irs)
+    h, hl = CL.pack(irs, ir_lens, "alter_drr")
     prep = _prepare(h, hl, hl, rate, drr, True, "alter_drr")
-    return _result(prep["ir"], hl, as_list, shape)
+    return CL.unpack(prep["ir"], hl, irs)
 
 
 @torch.no_grad()
 def measure_drr(irs, rate, ir_lens=None):
     """EffectMixin.measure_drr: the direct-to-reverberant ratio in dB of each impulse response -> fp32 [B] on the device.  (It and
     alter_drr go through mmx_ir_prepare whole, table included, so they refuse what convolve refuses: more than MAX_TAPS taps.)"""
-    h, hl = _clips(irs, ir_lens, "measure_drr")
+    CL.on_device("measure_drr", irs)
+    h, hl = CL.pack(irs, ir_lens, "measure_drr")
     return _prepare(h, hl, hl, rate, None, True, "measure_drr")["drr"]
 
 
@@ -356,37 +292,34 @@ def mix(clips, noises, rate, snr=10.0, lens=None, noise_lens=None):
     loudness, mmx.loudness with partial="pad", each clip alone) and the noise is added at `snr` dB (one value, or one per clip)
     below the clip.  `rate` must be one the meter supports.  Result as convolve."""
     from . import loudness as LOUD
-    as_list = not isinstance(clips, torch.Tensor)
-    shape = None if as_list else tuple(clips.shape)
-    x, lens = _clips(clips, lens, "mix")
+    CL.on_device("mix", clips, noises)
+    x, lens = CL.pack(clips, lens, "mix")
     B, L = x.shape
-    if isinstance(noises, torch.Tensor) and noises.dim() == 1:
-        noises = [noises]
-    nz, nl = _clips(noises, noise_lens, "mix (noise)")
+    nz, nl = CL.pack(noises, noise_lens, "mix (noise)")
+    if min(lens + nl) < 1:
+        raise MmxError("mix: an empty clip")
     if nz.shape[0] not in (1, B):
         raise ValueError(f"mix: one noise clip, or one per clip ({B}), got {nz.shape[0]}")
-    snrs = torch.tensor(_per_clip(snr, B, "mix: snr"), dtype=torch.float32, device=x.device)
+    snrs = torch.tensor(CL.per_clip(snr, B, "mix: snr"), dtype=torch.float32, device=x.device)
     fit = torch.zeros(B, L, dtype=torch.float32, device=x.device)                # effects.py:54-56: pad, then truncate
     for b in range(B):
         src = 0 if nz.shape[0] == 1 else b
         m = min(nl[src], lens[b])
         fit[b, :m] = nz[src, :m]
-    ragged = None if all(v == L for v in lens) else lens
-    lx = LOUD._run(x, ragged, rate, partial="pad")["lufs"]
-    ln = LOUD._run(fit, ragged, rate, partial="pad")["lufs"]
-    return _result(mix_rows(x, fit, lx, ln, snrs, lens), lens, as_list, shape)
+    lx = LOUD._run(x, lens, rate, partial="pad")["lufs"]
+    ln = LOUD._run(fit, lens, rate, partial="pad")["lufs"]
+    return CL.unpack(mix_rows(x, fit, lx, ln, snrs, lens), lens, clips)
 
 
 def mix_rows(x, noise, lx, ln, snr, lens=None, noise_lens=None):
     """mmx_mix_rows: x, noise fp32 [B, L] / [B, Ln], lx, ln, snr fp32 [B], all on the device -> fp32 [B, L], zero past lens."""
-    if not (x.is_cuda and noise.is_cuda and lx.is_cuda and ln.is_cuda and snr.is_cuda):
-        raise MmxError("mix_rows works on device memory only (no CPU fallback)")
+    CL.on_device("mix_rows", x, noise, lx, ln, snr)
     B, L = x.shape
     dev = x.device
-    d_lens = None if lens is None or all(v == L for v in lens) else torch.tensor(lens, dtype=torch.int32, device=dev)
-    d_nl = None if noise_lens is None else torch.tensor([int(v) for v in noise_lens], dtype=torch.int32, device=dev)
+    d_lens, _ = CL.lens_args(lens, L, dev)
+    d_nl, _ = CL.lens_args(noise_lens, noise.shape[1], dev)
     out = torch.empty(B, L, dtype=torch.float32, device=dev)
-    check(load().mmx_mix_rows(_p(x), _bs(x), L, B, _p(d_lens), _p(noise), _bs(noise), noise.shape[1], _p(d_nl), _p(lx), _p(ln), _p(snr),
+    check(load().mmx_mix_rows(_p(x), CL.row_stride(x), L, B, _p(d_lens), _p(noise), CL.row_stride(noise), noise.shape[1], _p(d_nl), _p(lx), _p(ln), _p(snr),
                               _p(out), i64(L), stream()), "mmx_mix_rows")
     return out
 

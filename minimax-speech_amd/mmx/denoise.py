@@ -27,10 +27,10 @@ import math
 
 import torch
 
+from . import clips as CL
 from . import mel as MEL
 from . import ops
 from ._lib import MmxError, check, i64, load, stream, _p
-from .loudness import _batch
 
 LDS_BYTES = 160 * 1024
 FRAMES_PER_TILE, GAP, CHUNK = 32, 16, 17                 # csrc/denoise.hip: GT_ROWS (two 16-frame tiles of spec_tile.h), GT_GAP, GT_CHUNK
@@ -125,47 +125,14 @@ def smoothing_taps(n_freq=3, n_time=5):
     return torch.outer(f, t) / float((n_freq + 1) ** 2 * (n_time + 1) ** 2)
 
 
-_tables = {}
-
-
 def _device_tables(n, dev):
     """(forward basis planes, inverse planes of [n, real columns | imaginary columns], fp32 window) on `dev`, built once per
     (n, device)."""
-    key = (int(n), str(dev))
-    if key not in _tables:
-        _tables[key] = (MEL.packed3(forward_basis(n), dev), MEL.packed3(torch.cat(inverse_table(n), dim=1), dev), window(n).to(dev))
-    return _tables[key]
+    return CL.device_tables(("denoise", int(n), str(dev)), lambda: (
+        MEL.packed3(forward_basis(n), dev), MEL.packed3(torch.cat(inverse_table(n), dim=1), dev), window(n).to(dev)))
 
 
 # ------------------------------------------------------------------------------------------------ launches
-def _clips(clips, lens, what):
-    """(fp32 [B, L] with unit stride along L, lens or None) of a list of mono clips or a padded batch [B, L] / [B, 1, L] / [n]."""
-    if isinstance(clips, torch.Tensor):
-        if clips.dim() == 3 and clips.shape[1] == 1:
-            clips = clips[:, 0]
-        elif clips.dim() == 3:
-            raise ValueError(f"{what}: mono clips only, got {tuple(clips.shape)}")
-        items = [clips]
-    else:
-        clips = [w.reshape(-1) for w in clips]
-        items = clips
-        if not items:
-            raise ValueError(f"{what}: no clips")
-    if not all(w.is_cuda for w in items):
-        raise MmxError(f"{what} works on device memory only (no CPU fallback)")
-    return _batch(clips, lens)
-
-
-def _lens_args(lens, B, dev):
-    if lens is None:
-        return None, None
-    return torch.tensor(lens, dtype=torch.int32, device=dev), (C.c_int32 * B)(*lens)
-
-
-def _bs(t):
-    return i64(t.stride(0) if t.shape[0] > 1 else t.shape[1])
-
-
 def _refuse(what, lens, n, hop, n_freq=3, n_time=5):
     why = refusal(lens, n, hop, n_freq, n_time)
     if why:
@@ -176,11 +143,11 @@ def _threshold(x, lens, n_std, n):
     """x fp32 [B, L] on the device (rows may be views into longer rows) -> fp32 [B, bins]."""
     B, L = x.shape
     basis, _, _ = _device_tables(n, x.device)
-    d_lens, h_lens = _lens_args(lens, B, x.device)
+    d_lens, h_lens = CL.lens_args(lens, L, x.device)
     cap = -(-frames_of(L, n) // FRAMES_PER_TILE)
     work = torch.empty(B, cap, padded_bins(n), 2, dtype=torch.float64, device=x.device)
     out = torch.empty(B, n // 2 + 1, dtype=torch.float32, device=x.device)
-    check(load().mmx_gate_threshold(_p(x), _bs(x), L, B, _p(d_lens), h_lens, _p(basis), n, C.c_double(float(n_std)), _p(work), cap,
+    check(load().mmx_gate_threshold(_p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(basis), n, C.c_double(float(n_std)), _p(work), cap,
                                     _p(out), i64(out.shape[1]), stream()), "mmx_gate_threshold")
     return out
 
@@ -190,8 +157,9 @@ def gate_threshold(noise, lens=None, n_std=3.0, win_length=2048, hop_length=512)
     """The gate's per-bin threshold in dB of noise clips (a list of mono clips, one clip [n], or a padded batch [B, L] with `lens`):
     mean + n_std * unbiased std over each clip's own frames of 20 log10 max(|STFT|, 1e-4) -> fp32 [B, win_length // 2 + 1] on the
     device.  Sums and finish are fp64 in a fixed order: a clip's row is that of its solo run, bit for bit."""
-    x, lens = _clips(noise, lens, "gate_threshold")
-    _refuse("gate_threshold", lens or [x.shape[1]], win_length, hop_length)
+    CL.on_device("gate_threshold", noise)
+    x, lens = CL.pack(noise, lens, "gate_threshold")
+    _refuse("gate_threshold", lens, win_length, hop_length)
     return _threshold(x, lens, n_std, int(win_length))
 
 
@@ -209,49 +177,41 @@ def spectral_gate(clips, noise, lens=None, denoise_amount=1.0, n_std=3.0, win_le
     or one per clip.  Returns the gated clips: a list of [n] views for a list, a tensor of the input's shape (zero past `lens`) for a
     tensor; with return_mask also the list of the binary masks, bool [bins, frames] per clip (True: gated).  MmxError where refusal()
     gives a reason: nothing is launched then.  Nothing is read back; a clip's result is that of its solo run, bit for bit."""
-    as_list = not isinstance(clips, torch.Tensor)
-    shape = None if as_list else tuple(clips.shape)
-    x, lens = _clips(clips, lens, "spectral_gate")
+    CL.on_device("spectral_gate", clips, noise)
+    x, lens = CL.pack(clips, lens, "spectral_gate")
     B, L = x.shape
     n, dev = int(win_length), x.device
-    own = lens or [L] * B
-    _refuse("spectral_gate", own, n, hop_length, n_freq, n_time)
+    _refuse("spectral_gate", lens, n, hop_length, n_freq, n_time)
     if _is_span(noise):
         a, b = noise
-        if not 0 <= a < b <= min(own):
-            raise MmxError(f"spectral_gate: the noise span ({a}, {b}) does not lie inside a clip of {min(own)} samples")
+        if not 0 <= a < b <= min(lens):
+            raise MmxError(f"spectral_gate: the noise span ({a}, {b}) does not lie inside a clip of {min(lens)} samples")
         _refuse("spectral_gate (noise span)", [b - a], n, hop_length)
         thresh = _threshold(x[:, a:b], None, n_std, n)
     else:
-        shared = isinstance(noise, torch.Tensor)
-        nz, nlens = _clips(noise[None] if shared and noise.dim() == 1 else noise, None, "spectral_gate (noise)")
-        if nz.shape[0] != (1 if shared else B):
+        nz, nlens = CL.pack(noise, None, "spectral_gate (noise)")
+        if nz.shape[0] != (1 if isinstance(noise, torch.Tensor) else B):
             raise ValueError(f"spectral_gate: noise is one clip, one per clip ({B}) or a (start, stop) span, got {nz.shape[0]} clips")
-        _refuse("spectral_gate (noise)", nlens or [nz.shape[1]], n, hop_length)
+        _refuse("spectral_gate (noise)", nlens, n, hop_length)
         thresh = _threshold(nz, nlens, n_std, n)
-    amt = denoise_amount
-    if not isinstance(amt, torch.Tensor):
-        amt = torch.tensor([float(v) for v in amt] if isinstance(amt, (list, tuple)) else [float(amt)] * B, dtype=torch.float32)
-    amt = amt.to(dev, torch.float32).reshape(-1).contiguous()
-    if amt.numel() != B:
-        raise ValueError(f"spectral_gate: denoise_amount is one value or one per clip ({B})")
+    amt = torch.tensor(CL.per_clip(denoise_amount, B, "spectral_gate: denoise_amount"), dtype=torch.float32, device=dev)
 
     basis, inv, win = _device_tables(n, dev)
-    d_lens, h_lens = _lens_args(lens, B, dev)
+    d_lens, h_lens = CL.lens_args(lens, L, dev)
     nbp, fcap = padded_bins(n), frames_of(L, n)
     spec = torch.empty(B, fcap, 2 * nbp, dtype=torch.float32, device=dev)
     mask = torch.empty(B, fcap, nbp, dtype=torch.uint8, device=dev)
     frames = torch.empty(B, fcap, n, dtype=torch.float32, device=dev)
     out = torch.empty(B, L, dtype=torch.float32, device=dev)
     lib = load()
-    check(lib.mmx_gate_analyze(_p(x), _bs(x), L, B, _p(d_lens), h_lens, _p(basis), n, _p(thresh),
+    check(lib.mmx_gate_analyze(_p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(basis), n, _p(thresh),
                                i64(thresh.shape[1] if thresh.shape[0] > 1 else 0), _p(spec), _p(mask), fcap, stream()), "mmx_gate_analyze")
     check(lib.mmx_gate_synthesize(_p(spec), _p(mask), fcap, L, B, _p(d_lens), h_lens, _p(inv), _p(win), n, int(n_freq), int(n_time),
                                   _p(amt), _p(frames), _p(out), i64(L), stream()), "mmx_gate_synthesize")
-    res = [out[b, :v] for b, v in enumerate(own)] if as_list else out.reshape(shape if len(shape) > 1 else (L,))
+    res = CL.unpack(out, lens, clips)
     if not return_mask:
         return res
-    return res, [mask[b, :frames_of(v, n), :n // 2 + 1].t().bool() for b, v in enumerate(own)]
+    return res, [mask[b, :frames_of(v, n), :n // 2 + 1].t().bool() for b, v in enumerate(lens)]
 
 
 class SpectralGate(torch.nn.Module):

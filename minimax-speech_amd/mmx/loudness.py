@@ -35,6 +35,7 @@ import math
 import numpy as np
 import torch
 
+from . import clips as CL
 from ._lib import MmxError, check, i64, load, stream, _p
 
 MIN_LOUDNESS = -70.0
@@ -133,23 +134,18 @@ def _cap(L, rate, S):
     return -(-max(int(L), rate // 2 + 1) // S)
 
 
-_tables = {}
-
-
 def _device_tables(rate, dev):
-    key = (int(rate), str(dev))
-    if key not in _tables:
+    def build():
         tab, seg = tables(rate)
-        _tables[key] = (torch.from_numpy(tab).to(dev), seg)
-    return _tables[key]
+        return torch.from_numpy(tab).to(dev), seg
+    return CL.device_tables(("loudness", int(rate), str(dev)), build)
 
 
 def _run(wave, lens, rate, nch=1, partial="pad", G=None, db=None, max_peak=1.0, want_mask=False, scale=False):
     """The one place that launches.  wave fp32 [rows, L] on the device (unit stride along L; a clip is `nch` adjacent rows),
     lens a list of ints per row or None -> dict(lufs fp32 [clips], peak fp32 [rows], energy f64 [rows, cap], and, with db,
     gain fp32 [clips]; with want_mask, mask uint8 [clips, cap - 3]; with scale, out fp32 [rows, L], written within lens only)."""
-    if not wave.is_cuda:
-        raise MmxError("mmx_kweight_blocks works on device memory only (no CPU fallback)")
+    CL.on_device("loudness", wave)
     rate = int(rate)
     _, S = block_sizes(rate)
     tab, seg = _device_tables(rate, wave.device)
@@ -159,7 +155,7 @@ def _run(wave, lens, rate, nch=1, partial="pad", G=None, db=None, max_peak=1.0, 
     if L < 1:
         raise ValueError("loudness: empty clips")
     clips, dev, code = rows // nch, wave.device, PARTIAL[partial]
-    d_lens = None if lens is None else torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
+    d_lens, _ = CL.lens_args(lens, L, dev)
     cap = _cap(L, rate, S)
     work = torch.empty(rows, cap, 5, dtype=torch.float64, device=dev)
     energy = torch.empty(rows, cap, dtype=torch.float64, device=dev)
@@ -167,7 +163,7 @@ def _run(wave, lens, rate, nch=1, partial="pad", G=None, db=None, max_peak=1.0, 
     lufs = torch.empty(clips, dtype=torch.float32, device=dev)
     gain = torch.empty(clips, dtype=torch.float32, device=dev) if db is not None else None
     mask = torch.zeros(clips, max(1, cap - 3), dtype=torch.uint8, device=dev) if want_mask else None
-    lib, bs = load(), i64(wave.stride(0) if rows > 1 else L)
+    lib, bs = load(), CL.row_stride(wave)
     check(lib.mmx_kweight_blocks(_p(wave), bs, L, rows, _p(d_lens), rate, code, _p(tab), seg, _p(work), cap, _p(energy), i64(cap),
                                  _p(peak), stream()), "mmx_kweight_blocks")
     Gh = None if G is None else (C.c_double * nch)(*[float(g) for g in G][:nch])
@@ -181,37 +177,13 @@ def _run(wave, lens, rate, nch=1, partial="pad", G=None, db=None, max_peak=1.0, 
     return dict(lufs=lufs, peak=peak, energy=energy, gain=gain, mask=mask, out=out)
 
 
-def _batch(waves, lens):
-    """(fp32 [B, L] with unit stride along L, lens or None) of a ragged list of mono clips or of a padded batch [B, L] / [n]."""
-    if isinstance(waves, torch.Tensor):
-        w = waves[None] if waves.dim() == 1 else waves
-        if w.dim() != 2:
-            raise ValueError(f"loudness takes mono clips [n], a padded batch [B, L] or a list of clips, got {tuple(waves.shape)}")
-        if not w.is_cuda:
-            raise MmxError("mmx_kweight_blocks works on device memory only (no CPU fallback)")
-        w = w.to(torch.float32)
-        if lens is not None:
-            lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
-            assert len(lens) == w.shape[0] and all(0 <= v <= w.shape[1] for v in lens)
-        return (w if w.stride(1) == 1 else w.contiguous()), lens
-    ws = [w.reshape(-1) for w in waves]
-    if not all(w.is_cuda for w in ws):
-        raise MmxError("mmx_kweight_blocks works on device memory only (no CPU fallback)")
-    lens = [int(w.numel()) for w in ws]
-    if len(ws) == 1:
-        return ws[0].to(torch.float32).contiguous()[None], None
-    batch = torch.zeros(len(ws), max(lens), dtype=torch.float32, device=ws[0].device)
-    for b, w in enumerate(ws):
-        batch[b, :lens[b]] = w
-    return batch, lens
-
-
 @torch.no_grad()
 def integrated_loudness(waves, rate, lens=None, partial="pad"):
     """Integrated loudness (LUFS) of mono clips: a ragged list of [n] / [1, n] tensors, one clip [n], or a padded batch [B, L]
     with `lens` valid samples per row -> fp32 [B] on the device.  Every clip is metered alone: its value is that of its solo run,
     bit for bit."""
-    w, lens = _batch(waves, lens)
+    CL.on_device("integrated_loudness", waves)
+    w, lens = CL.pack(waves, lens, "integrated_loudness")
     return _run(w, lens, rate, partial=partial)["lufs"]
 
 
@@ -219,9 +191,11 @@ def integrated_loudness(waves, rate, lens=None, partial="pad"):
 def normalize(waves, rate, db, max_peak=1.0, partial="pad"):
     """audiotools' normalize(db) followed by ensure_max_of_audio(max_peak) for a ragged list of mono clips ([n] / [1, n]) ->
     (the list of scaled clips [n], views of one buffer; the measured LUFS fp32 [B] of the inputs).  No host sync."""
-    w, lens = _batch(list(waves), None)
+    waves = list(waves)
+    CL.on_device("normalize", waves)
+    w, lens = CL.pack(waves, None, "normalize")
     r = _run(w, lens, rate, partial=partial, db=db, max_peak=max_peak, scale=True)
-    return [r["out"][b, :n] for b, n in enumerate(lens or [w.shape[1]])], r["lufs"]
+    return CL.unpack(r["out"], lens, waves), r["lufs"]
 
 
 class Meter:
@@ -246,8 +220,7 @@ class Meter:
     def integrated_loudness(self, data, detail=False):
         """data [nb, nt, nch] (nch <= 5) or [nt] on the device -> LUFS fp32 [nb].  detail=True: the whole result of the launches
         (the kept-block mask among it) instead."""
-        if not data.is_cuda:
-            raise MmxError("mmx_kweight_blocks works on device memory only (no CPU fallback)")
+        CL.on_device("Meter.integrated_loudness", data)
         if data.dim() == 1:
             data = data[None, :, None]
         if data.dim() != 3 or data.shape[2] > MAX_CH:

@@ -8,12 +8,12 @@ There is no CPU fallback: a CPU tensor raises.
 
 mel_filterbank restates what `librosa.filters.mel` builds with its defaults (htk=False, norm="slaney") from that function's
 published definition; librosa itself is not a dependency (restated seams)."""
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
+from . import clips as CL
 from . import ops
 from ._lib import BF16, F32, MmxError, TORCH_DT, check, i64, load, stream, _p
 
@@ -166,21 +166,11 @@ class _LogMelTables:
         self.filt = packed3(filter_table(fb, self.bin0, self.n_bins), self.dev)
 
     def _run(self, wave, lens, gain, time_major, dtype, out):
-        if not wave.is_cuda:
-            raise MmxError(f"{self._entry} works on device memory only (no CPU fallback)")
-        wave = wave.to(torch.float32)
-        if wave.dim() == 1:
-            wave = wave[None]
-        if wave.stride(1) != 1:
-            wave = wave.contiguous()
+        CL.on_device(self._entry, wave)
+        wave, lens = CL.pack(wave, lens, self._entry)
         B, L = wave.shape
-        h_lens = d_lens = None
-        if lens is not None:
-            lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
-            assert len(lens) == B
-            h_lens = (C.c_int32 * B)(*lens)
-            d_lens = torch.tensor(lens, dtype=torch.int32, device=wave.device)
-        T = max(1, max(self.frames(n) for n in (lens or [L])))       # a member without a frame: the entry point refuses it
+        d_lens, h_lens = CL.lens_args(lens, L, wave.device)
+        T = max(1, max(self.frames(n) for n in lens))                # a member without a frame: the entry point refuses it
         if time_major:
             if out is None:
                 out = torch.empty(B, T, self.n_mels, dtype=TORCH_DT[dtype], device=wave.device)
@@ -192,7 +182,7 @@ class _LogMelTables:
             cm, tm = torch.empty(B, self.n_mels, T, device=wave.device), None
         if gain is not None:
             gain = gain.to(torch.float32).reshape(B).contiguous()
-        check(getattr(load(), self._entry)(_p(wave), i64(wave.stride(0) if B > 1 else L), L, B, *([_p(gain)] if self._takes_gain else []),
+        check(getattr(load(), self._entry)(_p(wave), CL.row_stride(wave), L, B, *([_p(gain)] if self._takes_gain else []),
                                            _p(d_lens), h_lens, _p(self.basis), _p(self.filt), self.n_fft, self.hop, self.bin0, self.n_bins,
                                            self.n_mels, _p(cm), i64(T), _p(tm), T, dtype, stream()), self._entry)
         return tm if time_major else cm

@@ -28,10 +28,10 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import clips as CL
 from . import mel as MEL
 from . import ops
-from ._lib import MmxError, check, i64, load, stream, _p
-from .loudness import _batch
+from ._lib import MmxError, check, load, stream, _p
 
 MEL_N_MELS = (5, 10, 20, 40, 80, 160, 320)               # dac-vae/loss.py:261-262
 MEL_WINDOWS = (32, 64, 128, 256, 512, 1024, 2048)
@@ -84,74 +84,30 @@ def mel_table(rate, n_fft, n_mels, fmin=0.0, fmax=None):
     return MEL.filter_table(MEL.mel_filterbank(rate, n_fft, n_mels, fmin, fmax), 0, n_fft // 2 + 1)
 
 
-_tables = {}
-_packed = MEL.packed3
-
-
 def _device_tables(rate, n_fft, n_mels, fmin, fmax, dev):
     """(basis planes, filter planes or None) on `dev`, built once per (n_fft) and per (rate, n_fft, n_mels, fmin, fmax)."""
-    kb = (int(n_fft), str(dev))
-    if kb not in _tables:
-        _tables[kb] = _packed(dft_basis(n_fft), dev)
+    basis = CL.device_tables(("metrics", int(n_fft), str(dev)), lambda: MEL.packed3(dft_basis(n_fft), dev))
     if not n_mels:
-        return _tables[kb], None
-    kf = (int(rate), int(n_fft), int(n_mels), float(fmin), None if fmax is None else float(fmax), str(dev))
-    if kf not in _tables:
-        _tables[kf] = _packed(mel_table(rate, n_fft, n_mels, fmin, fmax), dev)
-    return _tables[kb], _tables[kf]
-
-
-def _pair(est, ref, lens):
-    """Two ragged batches -> (x fp32 [B, L], y fp32 [B, L], lens list or None); ValueError unless clip b of both has one length."""
-    if isinstance(est, torch.Tensor) != isinstance(ref, torch.Tensor):
-        raise ValueError("estimate and reference come as two tensors or as two lists of clips")
-    if isinstance(est, torch.Tensor):
-        if est.dim() == 3 and est.shape[1] == 1:
-            est = est[:, 0]
-        if ref.dim() == 3 and ref.shape[1] == 1:
-            ref = ref[:, 0]
-        if tuple(est.shape) != tuple(ref.shape):
-            raise ValueError(f"estimate {tuple(est.shape)} and reference {tuple(ref.shape)} differ in shape")
-    else:
-        est, ref = list(est), list(ref)
-        le, lr = [int(w.numel()) for w in est], [int(w.numel()) for w in ref]
-        if le != lr:
-            raise ValueError(f"estimate and reference clips differ in length: {le} against {lr}")
-    if not all(w.is_cuda for w in ([est, ref] if isinstance(est, torch.Tensor) else est + ref)):
-        raise MmxError("mmx_spec_dist / mmx_wave_sums work on device memory only (no CPU fallback)")
-    x, lx = _batch(est, lens)
-    y, _ = _batch(ref, lens)
-    if x.shape[1] < 1:
-        raise ValueError("empty clips")
-    return x, y, lx
-
-
-def _lens_tensors(lens, B, dev):
-    if lens is None:
-        return None, None
-    return torch.tensor(lens, dtype=torch.int32, device=dev), (C.c_int32 * B)(*lens)
-
-
-def _bs(t):
-    return i64(t.stride(0) if t.shape[0] > 1 else t.shape[1])
+        return basis, None
+    kf = ("metrics", int(rate), int(n_fft), int(n_mels), float(fmin), None if fmax is None else float(fmax), str(dev))
+    return basis, CL.device_tables(kf, lambda: MEL.packed3(mel_table(rate, n_fft, n_mels, fmin, fmax), dev))
 
 
 def spec_dist(x, y, lens, rate, n_fft, n_mels=0, fmin=0.0, fmax=None, pow=1.0, clamp_eps=1e-5, d_lens=None, h_lens=None):
     """One scale: x, y fp32 [B, L] on the device (unit stride along L), lens a list of ints or None -> f64 [B, 2] on the device
     (d_log, d_mag).  n_mels = 0: the STFT bins themselves.  MmxError where refusal() gives a reason: nothing is launched then."""
-    if not (x.is_cuda and y.is_cuda):
-        raise MmxError("mmx_spec_dist works on device memory only (no CPU fallback)")
+    CL.on_device("mmx_spec_dist", x, y)
     B, L = x.shape
     why = refusal(lens or [L], n_fft, n_mels)            # the entry point's own conditions, with a reason; nothing is launched
     if why:
         raise MmxError(f"mmx_spec_dist: {why}")
     basis, filt = _device_tables(rate, n_fft, n_mels, fmin, fmax, x.device)
-    if lens is not None and d_lens is None:
-        d_lens, h_lens = _lens_tensors(lens, B, x.device)
+    if d_lens is None:
+        d_lens, h_lens = CL.lens_args(lens, L, x.device)
     cap = -(-frames_of(L, n_fft) // FRAMES_PER_TILE)
     work = torch.empty(B, cap, 2, dtype=torch.float64, device=x.device)
     out = torch.empty(B, 2, dtype=torch.float64, device=x.device)
-    check(load().mmx_spec_dist(_p(x), _bs(x), _p(y), _bs(y), L, B, _p(d_lens), h_lens, _p(basis), _p(filt), int(n_fft), int(n_mels),
+    check(load().mmx_spec_dist(_p(x), CL.row_stride(x), _p(y), CL.row_stride(y), L, B, _p(d_lens), h_lens, _p(basis), _p(filt), int(n_fft), int(n_mels),
                                C.c_double(float(clamp_eps)), C.c_double(float(pow)), _p(work), cap, _p(out), stream()), "mmx_spec_dist")
     return out
 
@@ -159,15 +115,14 @@ def spec_dist(x, y, lens, rate, n_fft, n_mels=0, fmin=0.0, fmax=None, pow=1.0, c
 def wave_sums(x, y, lens=None, clip=None, d_lens=None):
     """x, y fp32 [B, L] on the device -> f64 [B, 7]: sum x, y, x^2, y^2, x y, |x - y|, (x - y)^2 over each clip's own samples,
     x limited to [-clip, clip] first when clip is given."""
-    if not (x.is_cuda and y.is_cuda):
-        raise MmxError("mmx_wave_sums works on device memory only (no CPU fallback)")
+    CL.on_device("mmx_wave_sums", x, y)
     B, L = x.shape
-    if lens is not None and d_lens is None:
-        d_lens, _ = _lens_tensors(lens, B, x.device)
+    if d_lens is None:
+        d_lens, _ = CL.lens_args(lens, L, x.device)
     cap = -(-L // SAMPLES_PER_CHUNK)
     work = torch.empty(B, cap, 7, dtype=torch.float64, device=x.device)
     out = torch.empty(B, 7, dtype=torch.float64, device=x.device)
-    check(load().mmx_wave_sums(_p(x), _bs(x), _p(y), _bs(y), L, B, _p(d_lens), C.c_float(0.0 if clip is None else float(clip)),
+    check(load().mmx_wave_sums(_p(x), CL.row_stride(x), _p(y), CL.row_stride(y), L, B, _p(d_lens), C.c_float(0.0 if clip is None else float(clip)),
                                _p(work), cap, _p(out), stream()), "mmx_wave_sums")
     return out
 
@@ -195,8 +150,16 @@ def metrics_from_sums(s, n):
     return dict(l1=s[..., 5] / n, mse=mse, snr_db=10.0 * lib.log10(var / (mse + 1e-10)), sisdr_db=sisdr_from_sums(s, n))
 
 
-def _counts(x, lens, d_lens):
-    if lens is None:
+def _intake(est, ref, lens, what):
+    """(x, y, lens, device lengths, host lengths) of a public call: CL.pack_pair, whose ValueErrors come before the device-only
+    refusal, and one upload of the lengths for all the launches."""
+    x, y, lens = CL.pack_pair(est, ref, lens, what)
+    CL.on_device(what, x, y)
+    return (x, y, lens) + CL.lens_args(lens, x.shape[1], x.device)
+
+
+def _counts(x, d_lens):
+    if d_lens is None:
         return torch.full((x.shape[0],), float(x.shape[1]), dtype=torch.float64, device=x.device)
     return d_lens.double()
 
@@ -223,9 +186,8 @@ def mel_distance(est, ref, rate, lens=None, n_mels=MEL_N_MELS, window_lengths=ME
                  mag_weight=0.0, mel_fmin=0.0, mel_fmax=None):
     """MelSpectrogramLoss (dac-vae/loss.py:231-327, its defaults) per clip: est / ref two lists of mono clips or two padded
     tensors [B, L] / [B, 1, L] with `lens` -> f64 [B] on the device.  Nothing is read back."""
-    x, y, lens = _pair(est, ref, lens)
+    x, y, lens, d_lens, h_lens = _intake(est, ref, lens, "mel_distance")
     nw = len(window_lengths)
-    d_lens, h_lens = _lens_tensors(lens, x.shape[0], x.device)
     return _multi_scale(x, y, lens, d_lens, h_lens, rate, window_lengths, _per_scale(n_mels, nw, "n_mels"), _per_scale(mel_fmin, nw, "mel_fmin"),
                         _per_scale(mel_fmax, nw, "mel_fmax"), pow, clamp_eps, log_weight, mag_weight)
 
@@ -233,8 +195,7 @@ def mel_distance(est, ref, rate, lens=None, n_mels=MEL_N_MELS, window_lengths=ME
 @torch.no_grad()
 def stft_distance(est, ref, rate=None, lens=None, window_lengths=STFT_WINDOWS, pow=2.0, clamp_eps=1e-5, log_weight=1.0, mag_weight=1.0):
     """MultiScaleSTFTLoss (dac-vae/loss.py:142-228, its defaults) per clip -> f64 [B] on the device.  `rate` plays no part."""
-    x, y, lens = _pair(est, ref, lens)
-    d_lens, h_lens = _lens_tensors(lens, x.shape[0], x.device)
+    x, y, lens, d_lens, h_lens = _intake(est, ref, lens, "stft_distance")
     return _multi_scale(x, y, lens, d_lens, h_lens, rate, window_lengths, None, None, None, pow, clamp_eps, log_weight, mag_weight)
 
 
@@ -243,9 +204,8 @@ def waveform_distance(est, ref, lens=None, clip=None):
     """dict of f64 [B] device tensors: l1 (L1Loss), mse and snr_db = 10 log10(var(ref) / (mse + 1e-10)) (extract_dac_latents.py:94-95)
     and sisdr_db, SISDRLoss's ratio with its defaults (zero mean, scaling, eps 1e-8) as a POSITIVE number of dB: the reference's
     loss is its negative.  clip: the estimate is limited to [-clip, clip] first (the extractor clips its reconstruction to 1)."""
-    x, y, lens = _pair(est, ref, lens)
-    d_lens, _ = _lens_tensors(lens, x.shape[0], x.device)
-    return metrics_from_sums(wave_sums(x, y, lens, clip, d_lens), _counts(x, lens, d_lens))
+    x, y, lens, d_lens, h_lens = _intake(est, ref, lens, "waveform_distance")
+    return metrics_from_sums(wave_sums(x, y, lens, clip, d_lens), _counts(x, d_lens))
 
 
 @torch.no_grad()
@@ -253,11 +213,9 @@ def audio_distance(est, ref, rate, lens=None, clip=None):
     """What the reference's validation step and extractor say about a reconstruction, per clip: dict of f64 [B] device tensors
     mel (MelSpectrogramLoss as train.py configures it: pow 1, mag_weight 0, seven scales), stft (MultiScaleSTFTLoss with
     train.py's windows [1024, 2048]), l1, mse, snr_db, sisdr_db.  No value is read back."""
-    x, y, lens = _pair(est, ref, lens)
-    B = x.shape[0]
-    d_lens, h_lens = _lens_tensors(lens, B, x.device)
+    x, y, lens, d_lens, h_lens = _intake(est, ref, lens, "audio_distance")
     nw = len(MEL_WINDOWS)
     out = dict(mel=_multi_scale(x, y, lens, d_lens, h_lens, rate, MEL_WINDOWS, list(MEL_N_MELS), [0.0] * nw, [None] * nw, 1.0, 1e-5, 1.0, 0.0),
                stft=_multi_scale(x, y, lens, d_lens, h_lens, rate, VALIDATION_STFT_WINDOWS, None, None, None, 2.0, 1e-5, 1.0, 1.0))
-    out.update(metrics_from_sums(wave_sums(x, y, lens, clip, d_lens), _counts(x, lens, d_lens)))
+    out.update(metrics_from_sums(wave_sums(x, y, lens, clip, d_lens), _counts(x, d_lens)))
     return out

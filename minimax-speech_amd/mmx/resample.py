@@ -11,12 +11,12 @@ base = min(o, n) * rolloff and width = ceil(lowpass_filter_width * o / base), ou
 over the m with |t| < lowpass_filter_width, x = 0 outside the clip, ceil(n * L / o) outputs.  This module builds the taps in
 float64, rounds them once to fp32 and packs the live ones per phase; the arithmetic is the kernel's.  There is no CPU fallback:
 a CPU tensor raises MmxError."""
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
+from . import clips as CL
 from ._lib import MmxError, check, i64, load, stream, _p
 
 NOUT = 1024                                              # include/mmx_hip.h MMX_RESAMPLE_NOUT: outputs per workgroup
@@ -120,19 +120,16 @@ class Resample:
         return self._tables[dev]
 
     def _run(self, wave, lens):
-        """wave fp32 [B, L] on the device (unit stride along L), lens a list of ints or None -> [B, out_len(longest)]: the one place
-        that launches."""
+        """wave fp32 [B, L] on the device (unit stride along L), lens a list of B ints -> [B, out_len(longest)]: the one place that
+        launches."""
         B, L = wave.shape
         taps, first, count = self._device_tables(wave.device)
-        h_lens = d_lens = None
-        if lens is not None:
-            h_lens = (C.c_int32 * B)(*lens)
-            d_lens = torch.tensor(lens, dtype=torch.int32, device=wave.device)
-        cols = max(1, self.out_len(max(lens) if lens is not None else L))
+        d_lens, h_lens = CL.lens_args(lens, L, wave.device)
+        cols = max(1, self.out_len(max(lens)))
         if cols > 2 ** 31 - 1 - NOUT:
             raise MmxError(f"mmx_resample_sinc: {cols} output samples per clip do not fit the entry point's 32-bit column count")
         out = torch.empty(B, cols, dtype=torch.float32, device=wave.device)
-        check(load().mmx_resample_sinc(_p(wave), i64(wave.stride(0) if B > 1 else L), L, B, _p(d_lens), h_lens, self.o, self.n,
+        check(load().mmx_resample_sinc(_p(wave), CL.row_stride(wave), L, B, _p(d_lens), h_lens, self.o, self.n,
                                        self._host[3], _p(taps), _p(first), _p(count), taps.shape[0], _p(out), i64(cols), cols, stream()),
               "mmx_resample_sinc")
         return out
@@ -143,35 +140,18 @@ class Resample:
         fp32 [out_len(n)] or [B, out_len(longest)], a shorter clip's remaining columns 0.  Equal rates: the input itself."""
         if self.orig_freq == self.new_freq:
             return wave
-        if not wave.is_cuda:
-            raise MmxError("mmx_resample_sinc works on device memory only (no CPU fallback)")
-        solo = wave.dim() == 1
-        w = wave.to(torch.float32)
-        if solo:
-            w = w[None]
-        if w.dim() != 2:
-            raise ValueError(f"Resample takes [n] or [B, L], got {tuple(wave.shape)}")
-        if w.stride(1) != 1:
-            w = w.contiguous()
-        if lens is not None:
-            lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
-            assert len(lens) == w.shape[0]
-        out = self._run(w, lens)
-        return out[0] if solo else out
+        CL.on_device("Resample", wave)
+        out = self._run(*CL.pack(wave, lens, "Resample"))
+        return out[0] if wave.dim() == 1 else out
 
 
 def resample(waves, orig, new):
     """A ragged list of mono clips ([n] or [1, n], on one device) -> the list of their resampled clips, one launch: views of one
     buffer, each cut to its clip's output length.  A clip's values are those of its own solo run, bit for bit."""
-    waves = [w.reshape(-1) for w in waves]
+    waves = list(waves)
     if int(orig) == int(new) or not waves:
-        return waves
-    if not all(w.is_cuda for w in waves):
-        raise MmxError("mmx_resample_sinc works on device memory only (no CPU fallback)")
+        return [w.reshape(-1) for w in waves]
+    CL.on_device("resample", waves)
     rs = Resample(orig, new)
-    lens = [int(w.numel()) for w in waves]
-    batch = torch.zeros(len(waves), max(lens), dtype=torch.float32, device=waves[0].device)
-    for b, w in enumerate(waves):
-        batch[b, :lens[b]] = w
-    out = rs(batch, lens)
-    return [out[b, :rs.out_len(n)] for b, n in enumerate(lens)]
+    x, lens = CL.pack(waves, None, "resample")
+    return CL.unpack(rs._run(x, lens), [rs.out_len(n) for n in lens], waves)

@@ -15,6 +15,7 @@ import torch
 from . import mel as MEL
 from . import ops
 from ._lib import BF16, F32, X2, X2W, MmxError, check, i64, is_split, load, stream, _p
+from .clips import on_device, pack
 
 SAMPLE_RATE, N_FFT, HOP, N_MELS = 16000, 400, 160, 128
 MAX_FRAMES = 3000                                        # model_v2.py:401: more mel frames than this select the windowed path
@@ -274,15 +275,11 @@ class SpeechTokenizerEngine:
     def tokenize(self, waves16k: List[torch.Tensor]) -> List[torch.Tensor]:
         """16 kHz clips (each [n] or [1, n] on the device) -> one int32 token tensor per clip: one zero-padded batch through
         mmx_logmel_w (the whole-clip mel, with its clip maximum, comes before any windowing), then quantize."""
-        waves = [w.reshape(-1) for w in waves16k]
-        if any(not w.is_cuda for w in waves):
-            raise MmxError("SpeechTokenizerEngine works on device memory only (no CPU fallback)")
-        lens = [int(w.numel()) for w in waves]
+        waves = list(waves16k)
+        on_device("SpeechTokenizerEngine", waves)
+        batch, lens = pack([w.to(self.dev) for w in waves], None, "SpeechTokenizerEngine.tokenize")
         if self._mel is None:
             self._mel = LogMelW(self.n_mels, self.dev)
-        batch = torch.zeros(len(waves), max(lens), device=self.dev)
-        for i, w in enumerate(waves):
-            batch[i, :lens[i]] = w.to(self.dev, torch.float32)
         frames = [frames_of(n) for n in lens]
         if max(frames) <= MAX_FRAMES:
             mt = self._mel(batch, lens=lens, time_major=True, dtype=F32, out=self._buffers(len(waves), max(frames))["mt"])

@@ -92,17 +92,12 @@ class SpeakerEncoderEngine:
         mean_pooling the padded frames of the shorter clips are masked out of the pooling (reference_mel_masks).
         mel: the LogMel setting (default: speech/config.yaml:183-191)."""
         from . import mel as MEL
+        from .clips import pack
         lm = mel if mel is not None else MEL.LogMel(device=self.dev)
         assert lm.n_mels == self.mel_dim
         segs, gains = zip(*(MEL.prepare_reference(w.to(self.dev), sample_rate) for w in waves))
-        lens = [s.shape[1] for s in segs]
-        if len(segs) == 1:
-            batch = segs[0]
-        else:
-            batch = torch.zeros(len(segs), max(lens), device=self.dev)
-            for i, s in enumerate(segs):
-                batch[i, :lens[i]] = s[0]
-        mt = lm(batch, lens=lens if len(segs) > 1 else None, gain=torch.cat(gains), time_major=True, dtype=self.dtype)
+        batch, lens = pack(segs, None, "embed_audio")
+        mt = lm(batch, lens=lens, gain=torch.cat(gains), time_major=True, dtype=self.dtype)
         mask = None
         if self.mean_pooling and len(segs) > 1:
             frames = torch.tensor([lm.frames(n) for n in lens], device=self.dev)

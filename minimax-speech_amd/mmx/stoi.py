@@ -34,8 +34,9 @@ result is that of its solo run, bit for bit.  There is no CPU fallback: a CPU te
 import numpy as np
 import torch
 
+from . import clips as CL
 from . import mel as MEL
-from . import metrics as M
+from . import ops
 from ._lib import MmxError, check, load, stream, _p
 from .resample import Resample
 
@@ -58,7 +59,7 @@ def spectral_frames(kept):
 
 
 def padded_bins():
-    return M.padded_bins(NFFT)
+    return ops.round_up(NFFT // 2 + 1, 32)
 
 
 def window():
@@ -110,22 +111,17 @@ def refusal(lens, sample_rate=FS, est_lens=None):
     return None
 
 
-_tables = {}
-
-
 def _device_tables(dev):
     """(basis planes, band-table planes, fp32 window) on `dev`, built once per device."""
-    key = str(dev)
-    if key not in _tables:
+    def build():
         assert band_edges()[-1][1] <= 16 * BIN_TILES
-        _tables[key] = (MEL.packed3(dft_basis(), dev), MEL.packed3(third_octave_table(), dev),
-                        torch.from_numpy(window().astype(np.float32)).to(dev))
-    return _tables[key]
+        return (MEL.packed3(dft_basis(), dev), MEL.packed3(third_octave_table(), dev),
+                torch.from_numpy(window().astype(np.float32)).to(dev))
+    return CL.device_tables(("stoi", str(dev)), build)
 
 
 def _refuse(what, x, lens):
-    if not x.is_cuda:
-        raise MmxError(f"{what} works on device memory only (no CPU fallback)")
+    CL.on_device(what, x)
     why = refusal(lens or [x.shape[1]])
     if why:
         raise MmxError(f"{what}: {why}")
@@ -136,13 +132,13 @@ def select(ref, lens=None, d_lens=None, h_lens=None):
     map int32 [B, cap] (source frame of kept frame i; -1 from F on), kept int32 [B], cap = frames_of(L))."""
     _refuse("mmx_stoi_select", ref, lens)
     B, L = ref.shape
-    if lens is not None and d_lens is None:
-        d_lens, h_lens = M._lens_tensors(lens, B, ref.device)
+    if d_lens is None:
+        d_lens, h_lens = CL.lens_args(lens, L, ref.device)
     _, _, win = _device_tables(ref.device)
     cap = frames_of(L)
     out = dict(energy=torch.zeros(B, cap, dtype=torch.float64, device=ref.device), mask=torch.empty(B, cap, dtype=torch.uint8, device=ref.device),
                map=torch.empty(B, cap, dtype=torch.int32, device=ref.device), kept=torch.empty(B, dtype=torch.int32, device=ref.device), cap=cap)
-    check(load().mmx_stoi_select(_p(ref), M._bs(ref), L, B, _p(d_lens), h_lens, _p(win), _p(out["energy"]), _p(out["mask"]), _p(out["map"]),
+    check(load().mmx_stoi_select(_p(ref), CL.row_stride(ref), L, B, _p(d_lens), h_lens, _p(win), _p(out["energy"]), _p(out["mask"]), _p(out["map"]),
                                  _p(out["kept"]), cap, stream()), "mmx_stoi_select")
     return out
 
@@ -153,12 +149,12 @@ def bands(est, ref, lens, sel, d_lens=None, h_lens=None):
     _refuse("mmx_stoi_bands", est, lens)
     _refuse("mmx_stoi_bands", ref, lens)
     B, L = ref.shape
-    if lens is not None and d_lens is None:
-        d_lens, h_lens = M._lens_tensors(lens, B, ref.device)
+    if d_lens is None:
+        d_lens, h_lens = CL.lens_args(lens, L, ref.device)
     basis, filt, win = _device_tables(ref.device)
     cap = sel["cap"]
     env = torch.zeros(B, 2, cap, 16, dtype=torch.float32, device=ref.device)
-    check(load().mmx_stoi_bands(_p(est), M._bs(est), _p(ref), M._bs(ref), L, B, _p(d_lens), h_lens, _p(win), _p(sel["map"]), _p(sel["kept"]),
+    check(load().mmx_stoi_bands(_p(est), CL.row_stride(est), _p(ref), CL.row_stride(ref), L, B, _p(d_lens), h_lens, _p(win), _p(sel["map"]), _p(sel["kept"]),
                                 _p(basis), _p(filt), _p(env), cap, stream()), "mmx_stoi_bands")
     return env
 
@@ -185,17 +181,17 @@ def stoi(est, ref, sample_rate, extended=False, lens=None, return_frames=False):
     why = refusal([FRAME + 1], sample_rate)
     if why:
         raise MmxError(f"stoi: {why}")
-    x, y, lens = M._pair(est, ref, lens)                 # x the estimate, y the reference; ValueError where the lengths differ
+    x, y, lens = CL.pack_pair(est, ref, lens, "stoi")    # x the estimate, y the reference; ValueError where the lengths differ
+    CL.on_device("stoi", x, y)
     rate = int(sample_rate)
     if rate != FS:
         rs = Resample(rate, FS)
-        own = lens or [x.shape[1]] * x.shape[0]
         x, y = rs(x, lens), rs(y, lens)
-        lens = None if lens is None else [rs.out_len(n) for n in own]
-    why = refusal(lens or [x.shape[1]])
+        lens = [rs.out_len(n) for n in lens]
+    why = refusal(lens)
     if why:
         raise MmxError(f"stoi: {why}")
-    d_lens, h_lens = M._lens_tensors(lens, x.shape[0], x.device)
+    d_lens, h_lens = CL.lens_args(lens, x.shape[1], x.device)
     sel = select(y, lens, d_lens, h_lens)
     d, frames = score(bands(x, y, lens, sel, d_lens, h_lens), sel["kept"], extended)
     return (d, frames) if return_frames else d

@@ -23,7 +23,7 @@ import torch
 
 import test_degrade_host as H
 import test_s3tok_host as S3
-from mmx import degrade as D
+from mmx import clips, degrade as D
 
 pytestmark = pytest.mark.gpu
 
@@ -153,7 +153,7 @@ def test_entry_points_keep_the_sentinel_outside_the_written_region():
     prep = D._prepare([h.cuda() for h in hs], None, lens, None, None, True, "test")
     out = torch.full((B, L + 9), 5.0, device="cuda")
     peak = torch.full((B + 2,), 5.0, device="cuda")
-    d_lens, h_lens = D._lens_args(lens, L, x.device)
+    d_lens, h_lens = clips.lens_args(lens, L, x.device)
     check(load().mmx_fir_rows(_p(x), i64(L), L, B, _p(d_lens), h_lens, _p(prep["table"]), prep["kcap"], _p(prep["p"]), _p(prep["s"]),
                               _p(prep["taps"]), 1, _p(out), i64(L + 9), _p(peak), stream()), "mmx_fir_rows")
     torch.cuda.synchronize()

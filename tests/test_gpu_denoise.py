@@ -134,7 +134,7 @@ def test_waveform_against_float64_with_the_device_mask(n):
 @pytest.mark.parametrize("n", H.WINDOWS)
 def test_workspace_padding_is_defined(n):
     """mmx_gate_analyze on prefilled workspaces: padded bins and the frames at or past a member's last carry mask 0."""
-    from mmx import denoise as D
+    from mmx import clips, denoise as D
     from mmx._lib import check, i64, load, stream, _p
     xs, nz = H.batch(n)
     x, lens = padded(xs)
@@ -142,7 +142,7 @@ def test_workspace_padding_is_defined(n):
     nbp, bins, fcap = D.padded_bins(n), n // 2 + 1, D.frames_of(L, n) + 3
     thresh = D.gate_threshold([z.cuda() for z in nz], **kw(n))
     basis, _, _ = D._device_tables(n, x.device)
-    d_lens, h_lens = D._lens_args(lens, B, x.device)
+    d_lens, h_lens = clips.lens_args(lens, L, x.device)
     spec = torch.full((B, fcap, 2 * nbp), float("nan"), device="cuda")
     mask = torch.full((B, fcap, nbp), 255, dtype=torch.uint8, device="cuda")
     check(load().mmx_gate_analyze(_p(x), i64(x.stride(0)), L, B, _p(d_lens), h_lens, _p(basis), n, _p(thresh), i64(bins), _p(spec), _p(mask),

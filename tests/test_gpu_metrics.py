@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import test_metrics_host as H
-from mmx import metrics as M
+from mmx import clips, metrics as M
 from mmx._lib import MmxError
 
 pytestmark = pytest.mark.gpu
@@ -50,7 +50,7 @@ def test_one_scale_against_float64(n_fft, n_mels, pw, log_w, mag_w):
     """Every fixture pair and every edge length as ONE ragged batch through one scale (solo runs give the same bits: below)."""
     est = [dev(H.clip(name)[:n]) for name, n in PAIRS]
     ref = [dev(H.clip("ref")[:n]) for _, n in PAIRS]
-    x, y, lens = M._pair(est, ref, None)
+    x, y, lens = clips.pack_pair(est, ref, None, "test")
     got = M.spec_dist(x, y, lens, RATE, n_fft, n_mels, pow=pw).cpu()
     for i, (name, n) in enumerate(PAIRS):
         want = H.spec_ref(H.clip(name)[:n], H.clip("ref")[:n], n_fft, n_mels, pow=pw)
@@ -126,7 +126,7 @@ def test_ragged_batch_equals_solo_runs_bit_for_bit():
     est = [dev(H.clip("codec")[:n]) for n in lengths]
     ref = [dev(H.clip("ref")[:n]) for n in lengths]
     batch = M.audio_distance(est, ref, RATE, clip=1.0)
-    x, y, lens = M._pair(est, ref, None)
+    x, y, lens = clips.pack_pair(est, ref, None, "test")
     # the same members behind other rows and other padding: a padded tensor with lens, rows reversed
     rev = M.audio_distance(x.flip(0).contiguous(), y.flip(0).contiguous(), RATE, lens=lens[::-1], clip=1.0)
     for i in range(len(lengths)):

@@ -104,7 +104,7 @@ def test_refusals():
     assert "sample rate" in S.refusal([4097], 22050.5)
     assert "differ in length" in S.refusal([4097, 5000], S.FS, [4097, 4999])
     x = torch.zeros(4097)
-    with pytest.raises(ValueError, match="differ in length"):            # metrics._pair, before anything touches a device
+    with pytest.raises(ValueError, match="differ in length"):            # clips.pack_pair, before anything touches a device
         S.stoi([x], [x[:4000]], 10000)
     with pytest.raises(MmxError, match="no CPU fallback"):
         S.stoi([x], [x], 10000)
