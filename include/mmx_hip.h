@@ -819,6 +819,38 @@ int mmx_row_absmax(const float* x, int64_t x_bs, int L, int B, const int32_t* le
 int mmx_mix_rows(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const float* noise, int64_t n_bs, int Ln,
                  const int32_t* nlens, const float* lx, const float* ln, const float* snr, float* out, int64_t o_bs, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Channel degradations (csrc/channel.hip; the definitions are stated in mmx/channel.py): what the reference's low_pass / high_pass
+ * (dac-vae/audiotools/core/dsp.py:153-215) and mel_filterbank / equalizer / clip_distortion / quantization / mulaw_quantization
+ * (core/effects.py:386-523) need beside mmx_ir_prepare / mmx_fir_rows, on a ragged batch of mono fp32 rows, without a host sync.
+ * lens / h_lens as above: int32 [B] in device memory with the same values in host memory, or both NULL; lengths lie in [1, L].
+ *
+ * mmx_pad_edge_rows: out[b][i] = x[b][clamp(i - half, 0, lens[b] - 1)] for i < lens[b] + 2 half (replicate padding; half may exceed
+ *   the clip), zeros from there to L + 2 half; out fp32 [B][o_bs >= L + 2 half], not x.  Output n of a filter of 2 half + 1 taps with
+ *   replicate padding is sample n + 2 half of mmx_fir_rows (wrap = 0, p = 0) over these rows.
+ * mmx_row_select: out fp32 [B][R] = the order statistics ranks[b][r] (0 = the smallest; int32 [B][R] in device memory, h_ranks the
+ *   same values in host memory; R <= 4) of x[b][0 .. lens[b]), exact: a radix select over the order-preserving integer image of the
+ *   bits in four counting launches of 8 bits and a finishing launch, whatever the data; -0 counts as +0 and comes back as +0.
+ *   nanflag int32 [B]: 1 where the row holds a NaN (its out values are NaN then), else 0.
+ *   work int32 [B][R][1032]: scratch (four histograms of 256 bins, the chosen prefixes), zeroed here.  Integer atomics only.
+ * mmx_clip_rows: stats fp32 [B][4] = (v[lo], v[hi]) of the lower and of the upper quantile, w f64 [B][2] the interpolation weights
+ *   (device memory) -> thr fp32 [B][2] = v[lo] + (v[hi] - v[lo]) w in fp64, rounded once;
+ *   out[b][j] = min(max(x[b][j], thr[b][0]), thr[b][1]) for j < lens[b], zeros from lens[b] to L.  Where nanflag[b] is set, thr and the
+ *   row's samples are NaN.  out may be x.
+ * mmx_quantize_rows: q int32 [B] channels per row (device; h_q the same values in host memory, each >= 2), mode 0:
+ *   2 floor((x + 1) / 2 q) / q - 1; mode 1 (mu-law, mu = q - 1): c = trunc((sign(x) log1p(mu |x|) / log1p(mu) + 1) / 2 mu + 0.5),
+ *   z = c / mu * 2 - 1, sign(z) (exp(|z| log1p(mu)) - 1) / mu.  fp64 per sample, rounded once; zeros from lens[b] to L.  out may be x.
+ * MMX_EARG, before anything is launched or written: a length outside [1, L], lens without h_lens, a stride below the stated one,
+ *   half < 0, a rank outside [0, lens[b]), R outside [1, 4], q < 2, a mode outside {0, 1}. */
+int mmx_pad_edge_rows(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, int half, float* out,
+                      int64_t o_bs, hipStream_t stream);
+int mmx_row_select(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, const int32_t* ranks,
+                   const int32_t* h_ranks, int R, float* out, int32_t* nanflag, int32_t* work, hipStream_t stream);
+int mmx_clip_rows(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, const float* stats,
+                  const double* w, const int32_t* nanflag, float* thr, float* out, int64_t o_bs, hipStream_t stream);
+int mmx_quantize_rows(const float* x, int64_t x_bs, int L, int B, const int32_t* lens, const int32_t* h_lens, int mode, const int32_t* q,
+                      const int32_t* h_q, float* out, int64_t o_bs, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

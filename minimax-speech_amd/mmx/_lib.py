@@ -40,6 +40,7 @@ SYMBOLS = [
     "mmx_spec_dist", "mmx_wave_sums", "mmx_gate_threshold", "mmx_gate_analyze", "mmx_gate_synthesize",
     "mmx_stoi_select", "mmx_stoi_bands", "mmx_stoi_score",
     "mmx_ir_prepare", "mmx_fir_rows", "mmx_row_absmax", "mmx_mix_rows",
+    "mmx_pad_edge_rows", "mmx_row_select", "mmx_clip_rows", "mmx_quantize_rows",
 ]
 
 

@@ -22,8 +22,11 @@ too, is the reference's behaviour.  measure_drr (effects.py:576-589): 10 log10(s
 mix (effects.py:52-63, 200-220): the noise zero padded or cut to its clip's length FIRST, then
     out = x + exp(((Lx - snr) - Ln) ln 10 / 20) * noise,    Lx, Ln = mmx.loudness.integrated_loudness (partial="pad"), each clip alone.
 
-Deliberately left out: `ir_eq` / `other_eq` (the equalizer needs julius' band split), `use_original_phase`, multi-channel clips, and
-looping a short noise clip (it is zero padded, as EffectMixin.mix itself does; the looping is the reference's file loader's).
+`ir_eq` (apply_ir; effects.py:155-156) and `noise_eq` (mix; the reference's `other_eq`, effects.py:57-58) are mel-band equalizer
+curves for the impulse response and for the fitted noise: mmx.channel.equalizer, before alter_drr and before the metering.
+
+Deliberately left out: `use_original_phase`, multi-channel clips, and looping a short noise clip (it is zero padded, as
+EffectMixin.mix itself does; the looping is the reference's file loader's).
 
 The one host table is the set of Hann windows (float64).  There is no CPU fallback: a CPU tensor raises MmxError before any device
 work."""
@@ -250,11 +253,16 @@ def convolve(clips, irs, lens=None, ir_lens=None, start_at_max=True, wrap=True):
 
 
 @torch.no_grad()
-def apply_ir(clips, irs, rate, drr=None, start_at_max=True, wrap=True, lens=None, ir_lens=None):
+def apply_ir(clips, irs, rate, drr=None, start_at_max=True, wrap=True, lens=None, ir_lens=None, ir_eq=None):
     """EffectMixin.apply_ir for a ragged batch: alter_drr where `drr` (one value, or one per clip with None entries) names a target,
-    convolve, then the rescale to the input's peak (effects.py:160-177, clamps of 1e-8).  Arguments and result as convolve."""
+    convolve, then the rescale to the input's peak (effects.py:160-177, clamps of 1e-8).  ir_eq: an equalizer curve [n_bands] (or one
+    per impulse response) applied to the impulse responses first (mmx.channel.equalizer; effects.py:155-156).  Arguments and result as
+    convolve."""
     CL.on_device("apply_ir", clips, irs)
     x, lens = CL.pack(clips, lens, "apply_ir")
+    if ir_eq is not None:
+        from .channel import equalizer
+        irs = equalizer(irs, ir_eq, rate, lens=ir_lens)
     prep = _prepare(irs, ir_lens, lens, rate, drr, start_at_max, "apply_ir")
     B, L = x.shape
     d_lens, _ = CL.lens_args(lens, L, x.device)
@@ -286,11 +294,12 @@ def measure_drr(irs, rate, ir_lens=None):
 
 
 @torch.no_grad()
-def mix(clips, noises, rate, snr=10.0, lens=None, noise_lens=None):
+def mix(clips, noises, rate, snr=10.0, lens=None, noise_lens=None, noise_eq=None):
     """EffectMixin.mix for a ragged batch: clips as convolve takes them; noises one clip [n] for all, a list with one per clip, or a
     padded batch with `noise_lens`.  Each noise is zero padded or cut to its clip's length, both are metered (BS.1770 integrated
     loudness, mmx.loudness with partial="pad", each clip alone) and the noise is added at `snr` dB (one value, or one per clip)
-    below the clip.  `rate` must be one the meter supports.  Result as convolve."""
+    below the clip.  noise_eq: an equalizer curve [n_bands] (or one per clip) applied to the fitted noise before it is metered
+    (mmx.channel.equalizer; the reference's other_eq, effects.py:57-58).  `rate` must be one the meter supports.  Result as convolve."""
     from . import loudness as LOUD
     CL.on_device("mix", clips, noises)
     x, lens = CL.pack(clips, lens, "mix")
@@ -306,6 +315,9 @@ def mix(clips, noises, rate, snr=10.0, lens=None, noise_lens=None):
         src = 0 if nz.shape[0] == 1 else b
         m = min(nl[src], lens[b])
         fit[b, :m] = nz[src, :m]
+    if noise_eq is not None:
+        from .channel import equalizer
+        fit = equalizer(fit, noise_eq, rate, lens=lens)
     lx = LOUD._run(x, lens, rate, partial="pad")["lufs"]
     ln = LOUD._run(fit, lens, rate, partial="pad")["lufs"]
     return CL.unpack(mix_rows(x, fit, lx, ln, snrs, lens), lens, clips)
@@ -332,8 +344,9 @@ class RoomImpulseResponse(torch.nn.Module):
         super().__init__()
         self.sample_rate, self.start_at_max, self.wrap = int(sample_rate), bool(start_at_max), bool(wrap)
 
-    def forward(self, audio, ir, drr=None, lens=None, ir_lens=None):
-        return apply_ir(audio, ir, self.sample_rate, drr=drr, start_at_max=self.start_at_max, wrap=self.wrap, lens=lens, ir_lens=ir_lens)
+    def forward(self, audio, ir, drr=None, lens=None, ir_lens=None, eq=None):
+        return apply_ir(audio, ir, self.sample_rate, drr=drr, start_at_max=self.start_at_max, wrap=self.wrap, lens=lens, ir_lens=ir_lens,
+                        ir_eq=eq)
 
 
 class BackgroundNoise(torch.nn.Module):
@@ -344,5 +357,5 @@ class BackgroundNoise(torch.nn.Module):
         super().__init__()
         self.sample_rate = int(sample_rate)
 
-    def forward(self, audio, noise, snr=10.0, lens=None, noise_lens=None):
-        return mix(audio, noise, self.sample_rate, snr=snr, lens=lens, noise_lens=noise_lens)
+    def forward(self, audio, noise, snr=10.0, lens=None, noise_lens=None, eq=None):
+        return mix(audio, noise, self.sample_rate, snr=snr, lens=lens, noise_lens=noise_lens, noise_eq=eq)

@@ -210,34 +210,57 @@ class TtsEngine:
         return out
 
     def _degrade(self, wavs, rates, degrade):
-        """Room and noise simulation of recordings before anything else sees them (mmx.degrade.apply_ir, then mmx.degrade.mix: the
-        reference's RoomImpulseResponse / BackgroundNoise transforms).  wavs: a list of mono clips [n] on the device at `rates`;
-        degrade: per clip None (the clip as it is: nothing is launched) or a dict with `ir` (an impulse response at the clip's rate;
-        optional `drr`, `wrap`, `start_at_max`) and / or `noise` with `snr` (default 10 dB).  The IR is applied first, then the noise.
-        The clips that share a rate and a setting form one launch sequence; each clip's result is that of its solo call, bit for
-        bit.  No host sync."""
+        """Room, noise and channel simulation of recordings before anything else sees them (mmx.degrade, mmx.channel: the
+        reference's RoomImpulseResponse / BackgroundNoise / LowPass / HighPass / Equalizer / ClippingDistortion / Quantization /
+        MuLawQuantization transforms).  wavs: a list of mono clips [n] on the device at `rates`; degrade: per clip None (the clip as
+        it is: nothing is launched) or a dict with at least one effect: `ir` (an impulse response at the clip's rate; optional `drr`,
+        `wrap`, `start_at_max`, `ir_eq`), `noise` (optional `snr`, default 10 dB, and `noise_eq`), `low_pass` / `high_pass` (a cutoff in
+        Hz), `eq` (an equalizer curve [n_bands]), `clip` (a percentile in [0, 1]), `quantize` / `mulaw` (channels).  The order is
+        room, noise, band limits (low pass, then high pass), equalizer, clipping, quantizer (uniform, then mu-law).  The clips that
+        share a rate and a setting form one launch sequence; each clip's result is that of its solo call, bit for bit.  No host
+        sync."""
+        from . import channel as CH
         from .degrade import apply_ir, mix
+        effects = ("ir", "noise", "low_pass", "high_pass", "eq", "clip", "quantize", "mulaw")
         out, groups = list(wavs), {}
         for i, d in enumerate(degrade):
             if d is None:
                 continue
             d = dict(d)
-            ir, nz = d.pop("ir", None), d.pop("noise", None)
+            e = {k: d.pop(k, None) for k in effects + ("ir_eq", "noise_eq")}
             drr, snr = d.pop("drr", None), d.pop("snr", 10.0)
             wrap, at_max = bool(d.pop("wrap", True)), bool(d.pop("start_at_max", True))
-            if d or (ir is None and nz is None):
-                raise ValueError(f"degrade: a dict with `ir` (drr, wrap, start_at_max) and / or `noise` (snr); got also {sorted(d)}")
+            if d or all(e[k] is None for k in effects) or (e["ir_eq"] is not None and e["ir"] is None) or \
+                    (e["noise_eq"] is not None and e["noise"] is None):
+                raise ValueError(f"degrade: a dict with at least one of {', '.join(effects)} (and drr, wrap, start_at_max, ir_eq with "
+                                 f"`ir`; snr, noise_eq with `noise`); got {sorted(k for k in e if e[k] is not None)} and {sorted(d)}")
             dev = lambda t: None if t is None else t.to(self.dev, torch.float32).reshape(-1)
-            groups.setdefault((int(rates[i]), ir is not None, nz is not None, wrap, at_max), []).append((i, dev(ir), drr, dev(nz), float(snr)))
-        for (rate, has_ir, has_noise, wrap, at_max), members in groups.items():
-            clips = [out[i] for i, *_ in members]
-            if has_ir:
-                drrs = [m[2] for m in members]
-                clips = apply_ir(clips, [m[1] for m in members], rate, drr=None if all(v is None for v in drrs) else drrs,
-                                 start_at_max=at_max, wrap=wrap)
-            if has_noise:
-                clips = mix(clips, [m[3] for m in members], rate, snr=[m[4] for m in members])
-            for (i, *_), w in zip(members, clips):
+            curve = lambda c: None if c is None else [float(v) for v in (c.reshape(-1).tolist() if hasattr(c, "reshape") else c)]
+            e.update(ir=dev(e["ir"]), noise=dev(e["noise"]), drr=drr, snr=float(snr), **{k: curve(e[k]) for k in ("eq", "ir_eq", "noise_eq")})
+            form = tuple(None if e[k] is None else len(e[k]) if isinstance(e[k], list) else True for k in effects + ("ir_eq", "noise_eq"))
+            groups.setdefault((int(rates[i]), form, wrap, at_max), []).append((i, e))
+        for (rate, _, wrap, at_max), members in groups.items():
+            clips, first = [out[i] for i, _ in members], members[0][1]
+            col = lambda k: [e[k] for _, e in members]
+            if first["ir"] is not None:
+                drrs = col("drr")
+                clips = apply_ir(clips, col("ir"), rate, drr=None if all(v is None for v in drrs) else drrs, start_at_max=at_max,
+                                 wrap=wrap, ir_eq=None if first["ir_eq"] is None else col("ir_eq"))
+            if first["noise"] is not None:
+                clips = mix(clips, col("noise"), rate, snr=col("snr"), noise_eq=None if first["noise_eq"] is None else col("noise_eq"))
+            if first["low_pass"] is not None:
+                clips = CH.low_pass(clips, col("low_pass"), rate)
+            if first["high_pass"] is not None:
+                clips = CH.high_pass(clips, col("high_pass"), rate)
+            if first["eq"] is not None:
+                clips = CH.equalizer(clips, col("eq"), rate)
+            if first["clip"] is not None:
+                clips = CH.clip_distortion(clips, col("clip"))
+            if first["quantize"] is not None:
+                clips = CH.quantization(clips, col("quantize"))
+            if first["mulaw"] is not None:
+                clips = CH.mulaw_quantization(clips, col("mulaw"))
+            for (i, _), w in zip(members, clips):
                 out[i] = w
         return out
 
@@ -337,7 +360,9 @@ class TtsEngine:
         gate runs at the clip's own rate BEFORE the level matching, so the meter hears the cleaned speech.
         degrade: None (nothing is launched), or a dict with `ir` (plus optional `drr`, `wrap`, `start_at_max`) and / or `noise` plus
         `snr`: the room and the noise of mmx.degrade (_degrade), at the clip's own rate, IR first and then noise, BEFORE denoise and
-        the level matching - so a degraded and then cleaned prompt is expressible."""
+        the level matching - so a degraded and then cleaned prompt is expressible.  The dict also takes the channel effects of
+        mmx.channel, applied after room and noise in this order: `low_pass`, `high_pass` (Hz), `eq` (a curve [n_bands]), `clip` (a
+        percentile), `quantize`, `mulaw` (channels); and `ir_eq` / `noise_eq`, equalizer curves for the IR and the noise."""
         from .resample import Resample
         w = wave.to(self.dev, torch.float32).reshape(-1)
         if degrade is not None:

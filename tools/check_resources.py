@@ -34,6 +34,7 @@ GATED = [
     "gate_stft_kernel", "gate_thresh_kernel", "gate_synth_kernel", "gate_ola_kernel",
     "stoi_energy_kernel", "stoi_scan_kernel", "stoi_bands_kernel", "stoi_score_kernel", "stoi_finish_kernel",
     "ir_prepare_kernel", "ir_table_kernel", "fir_rows_kernel", "row_absmax_kernel", "mix_rows_kernel",
+    "pad_edge_kernel", "row_select_kernel", "clip_rows_kernel", "quantize_rows_kernel",
 ]
 
 
