@@ -1,6 +1,7 @@
-"""ctypes binding of libmmx_hip.so (include/mmx_hip.h).  Thin: tensors in, raw pointers out."""
+"""ctypes binding of libmmx_hip.so.  Thin: tensors in, raw pointers out; the argument types are read from include/mmx_hip.h."""
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -31,17 +32,36 @@ def is_split(dtype):
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMX_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libmmx_hip.so")   # MMX_LIB: A/B of two builds
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "mmx_hip.h")
 
-SYMBOLS = [
-    "mmx_abi_version", "mmx_gemm_win", "mmx_gemm_win_tile", "mmx_rownorm", "mmx_groupnorm", "mmx_act_rows", "mmx_gather_rows", "mmx_copy2d", "mmx_est_pack",
-    "mmx_sinusoidal_emb", "mmx_cfg_euler", "mmx_attn_dense", "mmx_attn_flash_bf16", "mmx_attn_flash_fp8", "mmx_attn_relpos_bf16", "mmx_attn_relpos_x", "mmx_attn_flash_x", "mmx_attn_flash_xs", "mmx_conv_cout1_tanh", "mmx_conv_cin1", "mmx_vae_sample", "mmx_resample_linear", "mmx_prefetch4", "mmx_mask_rows",
-    "mmx_est_tail", "mmx_est_resnet", "mmx_dac_ru", "mmx_pack_skinny", "mmx_skinny_gemm", "mmx_skinny2", "mmx_decode_prep", "mmx_rope_kv_store", "mmx_paged_attn", "mmx_decode_attn", "mmx_decode_attn_fin", "mmx_swiglu", "mmx_sample_step",
-    "mmx_sample_step_tab", "mmx_logmel", "mmx_pool_rows", "mmx_logmel_w", "mmx_s3_rope_fsmn", "mmx_fsq_encode", "mmx_resample_sinc", "mmx_kweight_blocks", "mmx_loudness_gate", "mmx_scale_rows",
-    "mmx_spec_dist", "mmx_wave_sums", "mmx_gate_threshold", "mmx_gate_analyze", "mmx_gate_synthesize",
-    "mmx_stoi_select", "mmx_stoi_bands", "mmx_stoi_score",
-    "mmx_ir_prepare", "mmx_fir_rows", "mmx_row_absmax", "mmx_mix_rows",
-    "mmx_pad_edge_rows", "mmx_row_select", "mmx_clip_rows", "mmx_quantize_rows",
-]
+
+class MmxError(RuntimeError):
+    pass
+
+
+CTYPE_OF = {"hipStream_t": C.c_void_p, "int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+            "float": C.c_float, "double": C.c_double}
+
+
+def parse_header(path=HEADER_PATH):
+    """{entry point: [ctypes type of each parameter]} in the header's order: c_void_p for any pointer, else CTYPE_OF or an error."""
+    if not os.path.exists(path):
+        raise MmxError(f"{path} not found: the binding reads its argument types from it")
+    with open(path) as f:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+    sigs = {}
+    for name, params in re.findall(r"\bint\s+(mmx_\w+)\s*\(([^()]*)\)\s*;", text):
+        sigs[name] = types = []
+        for prm in ([] if params.strip() == "void" else params.split(",")):
+            ty = " ".join(w for w in prm.split()[:-1] if w != "const")      # the last word is the parameter's name
+            if "*" not in prm and ty not in CTYPE_OF:
+                raise MmxError(f"{path}: {name}: no ctypes type for parameter `{prm.strip()}`")
+            types.append(C.c_void_p if "*" in prm else CTYPE_OF[ty])
+    return sigs
+
+
+SIGNATURES = parse_header()
+SYMBOLS = list(SIGNATURES)
 
 
 class GemmParams(C.Structure):
@@ -93,11 +113,7 @@ def fill_struct(st, **kw):
 
 
 ABI_VERSION = 10                                         # include/mmx_hip.h: mmx_abi_version()
-_lib = None
-
-
-class MmxError(RuntimeError):
-    pass
+_lib, _fns = None, {}                                    # _fns: entry point -> (typed function, parameter count), filled by load()
 
 
 def load():
@@ -108,8 +124,10 @@ def load():
             raise MmxError(f"{LIB_PATH} not found: build it with `make -C minimax-speech_amd/csrc` "
                            "(or __graft_entry__.build()); the hot path has no CPU fallback")
         lib = C.CDLL(LIB_PATH)
-        for s in SYMBOLS:
-            getattr(lib, s).restype = C.c_int
+        for s, types in SIGNATURES.items():
+            fn = getattr(lib, s)
+            fn.restype, fn.argtypes = C.c_int, types
+            _fns[s] = fn, len(types)
         if lib.mmx_abi_version() != ABI_VERSION:         # a stale build: argument lists differ, refuse it
             raise MmxError(f"{LIB_PATH} has ABI version {lib.mmx_abi_version()}, this package binds version {ABI_VERSION}: "
                            "rebuild it (`make -C minimax-speech_amd/csrc`)")
@@ -117,17 +135,27 @@ def load():
     return _lib
 
 
+def call(name, *args):
+    """Typed call of entry point `name`: a wrong argument count or a non-zero return is an MmxError; an `int` past 2^31 - 1 is truncated."""
+    if _lib is None:
+        load()
+    fn, n = _fns[name]
+    if len(args) != n:
+        raise MmxError(f"{name} takes {n} arguments, {len(args)} given")
+    rc = fn(*args)
+    if rc:
+        check(rc, name)
+
+
 def _p(t):
-    if t is None:
-        return None
-    if isinstance(t, int):
-        return C.c_void_p(t)
+    if t is None or isinstance(t, int):
+        return t
     assert t.is_cuda, "libmmx_hip works on device memory only (no CPU fallback)"
-    return C.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 def check(rc, what):
@@ -167,6 +195,6 @@ TILES = {"auto": 0, "128x128": 1, "128x64": 2, "64x64": 3, "32x64": 4}
 def gemm_win(p, dtype, tile=0):
     """tile != 0 forces the block tile (mmx_gemm_win_tile; tuning tools only)."""
     if tile:
-        check(load().mmx_gemm_win_tile(C.byref(p), C.c_int(dtype), C.c_int(tile), stream()), "mmx_gemm_win_tile")
+        call("mmx_gemm_win_tile", C.byref(p), dtype, tile, stream())
     else:
-        check(load().mmx_gemm_win(C.byref(p), C.c_int(dtype), stream()), "mmx_gemm_win")
+        call("mmx_gemm_win", C.byref(p), dtype, stream())

@@ -43,7 +43,7 @@ import torch
 
 from . import clips as CL
 from . import degrade as D
-from ._lib import MmxError, check, i64, load, stream, _p
+from ._lib import MmxError, call, stream, _p
 
 ZEROS = 51                                               # dsp.py:153, 185
 BAND_ZEROS = 8                                           # julius.SplitBands
@@ -186,8 +186,7 @@ def pad_edge(x, lens, half):
     B, L = x.shape
     d_lens, h_lens = CL.lens_args(lens, L, x.device)
     out = torch.empty(B, L + 2 * half, dtype=torch.float32, device=x.device)
-    check(load().mmx_pad_edge_rows(_p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, int(half), _p(out), i64(L + 2 * half), stream()),
-          "mmx_pad_edge_rows")
+    call("mmx_pad_edge_rows", _p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, int(half), _p(out), L + 2 * half, stream())
     return out, [v + 2 * half for v in lens]
 
 
@@ -204,8 +203,7 @@ def _fir_padded(xp, plens, lens, L, taps, what):
     out = torch.zeros(B, L, dtype=torch.float32, device=xp.device)
     d_lens, _ = CL.lens_args(lens, L, xp.device)
     # the slice and prepare's scale undone in one launch: rows start 2 half samples into the product
-    check(load().mmx_scale_rows(_p(y.data_ptr() + 4 * 2 * half), i64(y.shape[1]), L, B, _p(d_lens), _p(gain), 1, _p(out), i64(L), stream()),
-          "mmx_scale_rows")
+    call("mmx_scale_rows", _p(y.data_ptr() + 4 * 2 * half), y.shape[1], L, B, _p(d_lens), _p(gain), 1, _p(out), L, stream())
     return out
 
 
@@ -324,8 +322,8 @@ def order_statistics(x, ranks, lens=None):
     vals = torch.empty(B, R, dtype=torch.float32, device=x.device)
     flag = torch.empty(B, dtype=torch.int32, device=x.device)
     work = torch.empty(B * R * SELECT_WORK, dtype=torch.int32, device=x.device)
-    check(load().mmx_row_select(_p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(d_ranks), _host_i32(flat), R, _p(vals), _p(flag),
-                                _p(work), stream()), "mmx_row_select")
+    call("mmx_row_select", _p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(d_ranks), _host_i32(flat), R, _p(vals), _p(flag),
+         _p(work), stream())
     return vals, flag
 
 
@@ -340,8 +338,7 @@ def _clip(x, lens, q, what):
     d_lens, h_lens = CL.lens_args(lens, L, x.device)
     thr = torch.empty(B, 2, dtype=torch.float32, device=x.device)
     out = torch.empty(B, L, dtype=torch.float32, device=x.device)
-    check(load().mmx_clip_rows(_p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(stats), _p(w), _p(flag), _p(thr), _p(out), i64(L),
-                               stream()), "mmx_clip_rows")
+    call("mmx_clip_rows", _p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(stats), _p(w), _p(flag), _p(thr), _p(out), L, stream())
     return thr, out
 
 
@@ -371,8 +368,8 @@ def _quantize(clips, channels, lens, mode, what):
     qs = [int(v) for v in qs]
     d_lens, h_lens = CL.lens_args(lens, L, x.device)
     out = torch.empty(B, L, dtype=torch.float32, device=x.device)
-    check(load().mmx_quantize_rows(_p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, mode, _p(torch.tensor(qs, dtype=torch.int32, device=x.device)),
-                                   _host_i32(qs), _p(out), i64(L), stream()), "mmx_quantize_rows")
+    call("mmx_quantize_rows", _p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, mode, _p(torch.tensor(qs, dtype=torch.int32, device=x.device)),
+         _host_i32(qs), _p(out), L, stream())
     return CL.unpack(out, lens, clips)
 
 

@@ -37,7 +37,7 @@ import torch
 
 from . import clips as CL
 from . import ops
-from ._lib import MmxError, check, i64, load, stream, _p
+from ._lib import MmxError, call, stream, _p
 
 LDS_BYTES = 160 * 1024
 WAVES, ROW_TILES = 4, 4                                  # csrc/degrade.hip: FIR_WAVES, FIR_RT (a row tile: 16 frames x 16 columns)
@@ -211,9 +211,9 @@ def _prepare(irs, ir_lens, sig_lens, rate, drr, start_at_max, what):
              s=torch.empty(B, dtype=torch.float32, device=dev), taps=torch.empty(B, dtype=torch.int32, device=dev),
              drr=torch.empty(B, dtype=torch.float32, device=dev), table=torch.empty(B, 3, kcap * 16, dtype=torch.bfloat16, device=dev),
              kcap=kcap, ir_lens=hl)
-    check(load().mmx_ir_prepare(_p(h), i64(0) if shared else CL.row_stride(h), Lir, B, _p(d_il), h_il, Lsig, _p(d_sl), h_sl, _p(d_drr), t0,
-                                _p(_hann(t0, dev)), int(bool(start_at_max)), _p(r["ir"]), i64(Lir), _p(r["p"]), _p(r["s"]),
-                                _p(r["taps"]), _p(r["drr"]), _p(r["table"]), kcap, stream()), "mmx_ir_prepare")
+    call("mmx_ir_prepare", _p(h), 0 if shared else CL.row_stride(h), Lir, B, _p(d_il), h_il, Lsig, _p(d_sl), h_sl, _p(d_drr), t0,
+         _p(_hann(t0, dev)), int(bool(start_at_max)), _p(r["ir"]), Lir, _p(r["p"]), _p(r["s"]), _p(r["taps"]), _p(r["drr"]),
+         _p(r["table"]), kcap, stream())
     return r
 
 
@@ -223,8 +223,8 @@ def _fir(x, lens, prep, wrap):
     d_lens, h_lens = CL.lens_args(lens, L, x.device)
     out = torch.empty(B, L, dtype=torch.float32, device=x.device)
     peak = torch.empty(B, dtype=torch.float32, device=x.device)
-    check(load().mmx_fir_rows(_p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(prep["table"]), prep["kcap"], _p(prep["p"]), _p(prep["s"]),
-                              _p(prep["taps"]), int(bool(wrap)), _p(out), i64(L), _p(peak), stream()), "mmx_fir_rows")
+    call("mmx_fir_rows", _p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(prep["table"]), prep["kcap"], _p(prep["p"]), _p(prep["s"]),
+         _p(prep["taps"]), int(bool(wrap)), _p(out), L, _p(peak), stream())
     return out, peak
 
 
@@ -234,7 +234,7 @@ def row_absmax(x, lens=None):
     B, L = x.shape
     d_lens, _ = CL.lens_args(lens, L, x.device)
     peak = torch.empty(B, dtype=torch.float32, device=x.device)
-    check(load().mmx_row_absmax(_p(x), CL.row_stride(x), L, B, _p(d_lens), _p(peak), stream()), "mmx_row_absmax")
+    call("mmx_row_absmax", _p(x), CL.row_stride(x), L, B, _p(d_lens), _p(peak), stream())
     return peak
 
 
@@ -270,7 +270,7 @@ def apply_ir(clips, irs, rate, drr=None, start_at_max=True, wrap=True, lens=None
     y, after = _fir(x, lens, prep, wrap)
     gain = before.clamp(min=1e-8) / after.clamp(min=1e-8)
     out = torch.zeros(B, L, dtype=torch.float32, device=x.device) if d_lens is not None else torch.empty_like(y)
-    check(load().mmx_scale_rows(_p(y), i64(L), L, B, _p(d_lens), _p(gain), 1, _p(out), i64(L), stream()), "mmx_scale_rows")
+    call("mmx_scale_rows", _p(y), L, L, B, _p(d_lens), _p(gain), 1, _p(out), L, stream())
     return CL.unpack(out, lens, clips)
 
 
@@ -331,8 +331,8 @@ def mix_rows(x, noise, lx, ln, snr, lens=None, noise_lens=None):
     d_lens, _ = CL.lens_args(lens, L, dev)
     d_nl, _ = CL.lens_args(noise_lens, noise.shape[1], dev)
     out = torch.empty(B, L, dtype=torch.float32, device=dev)
-    check(load().mmx_mix_rows(_p(x), CL.row_stride(x), L, B, _p(d_lens), _p(noise), CL.row_stride(noise), noise.shape[1], _p(d_nl), _p(lx), _p(ln), _p(snr),
-                              _p(out), i64(L), stream()), "mmx_mix_rows")
+    call("mmx_mix_rows", _p(x), CL.row_stride(x), L, B, _p(d_lens), _p(noise), CL.row_stride(noise), noise.shape[1], _p(d_nl), _p(lx),
+         _p(ln), _p(snr), _p(out), L, stream())
     return out
 
 

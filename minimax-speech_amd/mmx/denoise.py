@@ -22,7 +22,6 @@ silence.
 
 Tables are float64 -> three bf16 planes (mel.packed3), built once per (n, device).  There is no CPU fallback: a CPU tensor raises
 MmxError."""
-import ctypes as C
 import math
 
 import torch
@@ -30,7 +29,7 @@ import torch
 from . import clips as CL
 from . import mel as MEL
 from . import ops
-from ._lib import MmxError, check, i64, load, stream, _p
+from ._lib import MmxError, call, stream, _p
 
 LDS_BYTES = 160 * 1024
 FRAMES_PER_TILE, GAP, CHUNK = 32, 16, 17                 # csrc/denoise.hip: GT_ROWS (two 16-frame tiles of spec_tile.h), GT_GAP, GT_CHUNK
@@ -147,8 +146,8 @@ def _threshold(x, lens, n_std, n):
     cap = -(-frames_of(L, n) // FRAMES_PER_TILE)
     work = torch.empty(B, cap, padded_bins(n), 2, dtype=torch.float64, device=x.device)
     out = torch.empty(B, n // 2 + 1, dtype=torch.float32, device=x.device)
-    check(load().mmx_gate_threshold(_p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(basis), n, C.c_double(float(n_std)), _p(work), cap,
-                                    _p(out), i64(out.shape[1]), stream()), "mmx_gate_threshold")
+    call("mmx_gate_threshold", _p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(basis), n, float(n_std), _p(work), cap, _p(out),
+         out.shape[1], stream())
     return out
 
 
@@ -203,11 +202,10 @@ def spectral_gate(clips, noise, lens=None, denoise_amount=1.0, n_std=3.0, win_le
     mask = torch.empty(B, fcap, nbp, dtype=torch.uint8, device=dev)
     frames = torch.empty(B, fcap, n, dtype=torch.float32, device=dev)
     out = torch.empty(B, L, dtype=torch.float32, device=dev)
-    lib = load()
-    check(lib.mmx_gate_analyze(_p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(basis), n, _p(thresh),
-                               i64(thresh.shape[1] if thresh.shape[0] > 1 else 0), _p(spec), _p(mask), fcap, stream()), "mmx_gate_analyze")
-    check(lib.mmx_gate_synthesize(_p(spec), _p(mask), fcap, L, B, _p(d_lens), h_lens, _p(inv), _p(win), n, int(n_freq), int(n_time),
-                                  _p(amt), _p(frames), _p(out), i64(L), stream()), "mmx_gate_synthesize")
+    call("mmx_gate_analyze", _p(x), CL.row_stride(x), L, B, _p(d_lens), h_lens, _p(basis), n, _p(thresh),
+         thresh.shape[1] if thresh.shape[0] > 1 else 0, _p(spec), _p(mask), fcap, stream())
+    call("mmx_gate_synthesize", _p(spec), _p(mask), fcap, L, B, _p(d_lens), h_lens, _p(inv), _p(win), n, int(n_freq), int(n_time),
+         _p(amt), _p(frames), _p(out), L, stream())
     res = CL.unpack(out, lens, clips)
     if not return_mask:
         return res

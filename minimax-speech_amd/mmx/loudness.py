@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import clips as CL
-from ._lib import MmxError, check, i64, load, stream, _p
+from ._lib import MmxError, call, stream, _p
 
 MIN_LOUDNESS = -70.0
 G_BS1770 = (1.0, 1.0, 1.0, 1.41, 1.41)
@@ -163,17 +163,16 @@ def _run(wave, lens, rate, nch=1, partial="pad", G=None, db=None, max_peak=1.0, 
     lufs = torch.empty(clips, dtype=torch.float32, device=dev)
     gain = torch.empty(clips, dtype=torch.float32, device=dev) if db is not None else None
     mask = torch.zeros(clips, max(1, cap - 3), dtype=torch.uint8, device=dev) if want_mask else None
-    lib, bs = load(), CL.row_stride(wave)
-    check(lib.mmx_kweight_blocks(_p(wave), bs, L, rows, _p(d_lens), rate, code, _p(tab), seg, _p(work), cap, _p(energy), i64(cap),
-                                 _p(peak), stream()), "mmx_kweight_blocks")
+    bs = CL.row_stride(wave)
+    call("mmx_kweight_blocks", _p(wave), bs, L, rows, _p(d_lens), rate, code, _p(tab), seg, _p(work), cap, _p(energy), cap, _p(peak),
+         stream())
     Gh = None if G is None else (C.c_double * nch)(*[float(g) for g in G][:nch])
-    check(lib.mmx_loudness_gate(_p(energy), i64(cap), cap, _p(peak), _p(d_lens), L, clips, nch, Gh, rate, code, _p(lufs),
-                                int(db is not None), C.c_float(0.0 if db is None else float(db)), C.c_float(float(max_peak)), _p(gain),
-                                _p(mask), i64(mask.shape[1] if want_mask else 0), stream()), "mmx_loudness_gate")
+    call("mmx_loudness_gate", _p(energy), cap, cap, _p(peak), _p(d_lens), L, clips, nch, Gh, rate, code, _p(lufs), int(db is not None),
+         0.0 if db is None else float(db), float(max_peak), _p(gain), _p(mask), mask.shape[1] if want_mask else 0, stream())
     out = None
     if scale:
         out = torch.empty(rows, L, dtype=torch.float32, device=dev)
-        check(lib.mmx_scale_rows(_p(wave), bs, L, rows, _p(d_lens), _p(gain), nch, _p(out), i64(L), stream()), "mmx_scale_rows")
+        call("mmx_scale_rows", _p(wave), bs, L, rows, _p(d_lens), _p(gain), nch, _p(out), L, stream())
     return dict(lufs=lufs, peak=peak, energy=energy, gain=gain, mask=mask, out=out)
 
 

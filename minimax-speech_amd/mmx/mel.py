@@ -15,7 +15,7 @@ import torch
 
 from . import clips as CL
 from . import ops
-from ._lib import BF16, F32, MmxError, TORCH_DT, check, i64, load, stream, _p
+from ._lib import BF16, F32, MmxError, TORCH_DT, call, stream, _p
 
 LOG_CLIP = 1e-5                                          # audio.py:23 dynamic_range_compression_torch
 
@@ -182,9 +182,12 @@ class _LogMelTables:
             cm, tm = torch.empty(B, self.n_mels, T, device=wave.device), None
         if gain is not None:
             gain = gain.to(torch.float32).reshape(B).contiguous()
-        check(getattr(load(), self._entry)(_p(wave), CL.row_stride(wave), L, B, *([_p(gain)] if self._takes_gain else []),
-                                           _p(d_lens), h_lens, _p(self.basis), _p(self.filt), self.n_fft, self.hop, self.bin0, self.n_bins,
-                                           self.n_mels, _p(cm), i64(T), _p(tm), T, dtype, stream()), self._entry)
+        if self._takes_gain:
+            call("mmx_logmel", _p(wave), CL.row_stride(wave), L, B, _p(gain), _p(d_lens), h_lens, _p(self.basis), _p(self.filt),
+                 self.n_fft, self.hop, self.bin0, self.n_bins, self.n_mels, _p(cm), T, _p(tm), T, dtype, stream())
+        else:
+            call("mmx_logmel_w", _p(wave), CL.row_stride(wave), L, B, _p(d_lens), h_lens, _p(self.basis), _p(self.filt),
+                 self.n_fft, self.hop, self.bin0, self.n_bins, self.n_mels, _p(cm), T, _p(tm), T, dtype, stream())
         return tm if time_major else cm
 
 

@@ -23,15 +23,13 @@ Waveform, from the seven sums of mmx_wave_sums (n samples, x the estimate, y the
 
 mmx/mel.py builds the tables (float64; the window folded into the DFT basis); this module states the arithmetic around the launches.
 There is no CPU fallback: a CPU tensor raises MmxError."""
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import clips as CL
 from . import mel as MEL
 from . import ops
-from ._lib import MmxError, check, load, stream, _p
+from ._lib import MmxError, call, stream, _p
 
 MEL_N_MELS = (5, 10, 20, 40, 80, 160, 320)               # dac-vae/loss.py:261-262
 MEL_WINDOWS = (32, 64, 128, 256, 512, 1024, 2048)
@@ -107,8 +105,8 @@ def spec_dist(x, y, lens, rate, n_fft, n_mels=0, fmin=0.0, fmax=None, pow=1.0, c
     cap = -(-frames_of(L, n_fft) // FRAMES_PER_TILE)
     work = torch.empty(B, cap, 2, dtype=torch.float64, device=x.device)
     out = torch.empty(B, 2, dtype=torch.float64, device=x.device)
-    check(load().mmx_spec_dist(_p(x), CL.row_stride(x), _p(y), CL.row_stride(y), L, B, _p(d_lens), h_lens, _p(basis), _p(filt), int(n_fft), int(n_mels),
-                               C.c_double(float(clamp_eps)), C.c_double(float(pow)), _p(work), cap, _p(out), stream()), "mmx_spec_dist")
+    call("mmx_spec_dist", _p(x), CL.row_stride(x), _p(y), CL.row_stride(y), L, B, _p(d_lens), h_lens, _p(basis), _p(filt), int(n_fft),
+         int(n_mels), float(clamp_eps), float(pow), _p(work), cap, _p(out), stream())
     return out
 
 
@@ -122,8 +120,8 @@ def wave_sums(x, y, lens=None, clip=None, d_lens=None):
     cap = -(-L // SAMPLES_PER_CHUNK)
     work = torch.empty(B, cap, 7, dtype=torch.float64, device=x.device)
     out = torch.empty(B, 7, dtype=torch.float64, device=x.device)
-    check(load().mmx_wave_sums(_p(x), CL.row_stride(x), _p(y), CL.row_stride(y), L, B, _p(d_lens), C.c_float(0.0 if clip is None else float(clip)),
-                               _p(work), cap, _p(out), stream()), "mmx_wave_sums")
+    call("mmx_wave_sums", _p(x), CL.row_stride(x), _p(y), CL.row_stride(y), L, B, _p(d_lens), 0.0 if clip is None else float(clip),
+         _p(work), cap, _p(out), stream())
     return out
 
 

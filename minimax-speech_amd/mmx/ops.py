@@ -9,7 +9,7 @@ import math
 import torch
 
 from . import _lib as L
-from ._lib import ACT, BF16, F32, check, i64, load, stream, _p
+from ._lib import ACT, BF16, F32, call, stream, _p
 
 
 def round_up(x, m):
@@ -152,73 +152,66 @@ def rownorm(x, gamma, beta, eps, *, rows, C_, batch=1, x_bstride=None, rms=False
     ldx = C_ if ldx is None else ldx
     xb = rows * ldx if x_bstride is None else x_bstride
     ob = rows * C_ if o_bstride is None else o_bstride
-    check(load().mmx_rownorm(_p(x), i64(ldx), i64(xb), rows, C_, batch, _p(gamma), _p(beta), C.c_float(eps), int(rms),
-                             ACT[act], _p(rowmask), i64(rows if rm_bstride is None else rm_bstride), _p(addvec),
-                             i64(C_ if av_bstride is None else av_bstride), _p(out_f32), i64(C_), i64(ob), _p(out_act), i64(C_),
-                             i64(ob), dtype, stream()), "mmx_rownorm")
+    call("mmx_rownorm", _p(x), ldx, xb, rows, C_, batch, _p(gamma), _p(beta), eps, int(rms), ACT[act], _p(rowmask),
+         rows if rm_bstride is None else rm_bstride, _p(addvec), C_ if av_bstride is None else av_bstride, _p(out_f32), C_, ob,
+         _p(out_act), C_, ob, dtype, stream())
 
 
 def groupnorm(x, gamma, beta, out, *, B, T, C_, groups, dtype, eps=1e-5, act="none", rowmask=None):
-    check(load().mmx_groupnorm(_p(x), B, T, C_, groups, _p(gamma), _p(beta), C.c_float(eps), ACT[act], _p(rowmask), _p(out),
-                               dtype, stream()), "mmx_groupnorm")
+    call("mmx_groupnorm", _p(x), B, T, C_, groups, _p(gamma), _p(beta), eps, ACT[act], _p(rowmask), _p(out), dtype, stream())
 
 
 def act_rows(x, *, rows, C_, act="none", rowmask=None, out_f32=None, out_act=None, dtype=F32):
-    check(load().mmx_act_rows(_p(x), i64(rows), C_, ACT[act], _p(rowmask), _p(out_f32), _p(out_act), dtype, stream()),
-          "mmx_act_rows")
+    call("mmx_act_rows", _p(x), rows, C_, ACT[act], _p(rowmask), _p(out_f32), _p(out_act), dtype, stream())
 
 
 def mask_rows(x, rowmask, *, rows, C_, dtype):
     """x[row][:] = 0 where rowmask[row] == 0, in place (mmx_mask_rows)."""
-    check(load().mmx_mask_rows(_p(x), i64(rows), C_, _p(rowmask), dtype, stream()), "mmx_mask_rows")
+    call("mmx_mask_rows", _p(x), rows, C_, _p(rowmask), dtype, stream())
 
 
 def pool_rows(x, out, *, B, T, C_, dtype, mask=None):
     """out[b][:] = masked mean over the T rows of x [B][T][C] fp32 (mmx_pool_rows; mask fp32 [B][T] or None = plain mean)."""
-    check(load().mmx_pool_rows(_p(x), i64(T * C_), T, C_, B, _p(mask), i64(T), _p(out), i64(C_), dtype, stream()), "mmx_pool_rows")
+    call("mmx_pool_rows", _p(x), T * C_, T, C_, B, _p(mask), T, _p(out), C_, dtype, stream())
 
 
 def gather_rows(ids, table, *, scale=1.0, rowmask=None, out_f32=None, out_act=None, dtype=F32, ldo_f=None, ldo_a=None):
     n, C_ = ids.numel(), table.shape[1]
-    check(load().mmx_gather_rows(_p(ids), n, _p(table), C_, C.c_float(scale), _p(rowmask), _p(out_f32), i64(ldo_f or C_),
-                                 _p(out_act), i64(ldo_a or C_), dtype, stream()), "mmx_gather_rows")
+    call("mmx_gather_rows", _p(ids), n, _p(table), C_, scale, _p(rowmask), _p(out_f32), ldo_f or C_, _p(out_act), ldo_a or C_,
+         dtype, stream())
 
 
 def copy2d(src, src_dt, ibs, irs, ics, dst, dst_dt, obs, ors, ocs, rows, cols, batch=1, rep=1):
-    check(load().mmx_copy2d(_p(src), src_dt, i64(ibs), i64(irs), i64(ics), rep, _p(dst), dst_dt, i64(obs), i64(ors),
-                            i64(ocs), rows, cols, batch, stream()), "mmx_copy2d")
+    call("mmx_copy2d", _p(src), src_dt, ibs, irs, ics, rep, _p(dst), dst_dt, obs, ors, ocs, rows, cols, batch, stream())
 
 
 def est_pack(x, mu, spks, cond, h, *, B, T, dtype, x_bstride=None, x_mod=None):
-    check(load().mmx_est_pack(_p(x), i64(T * 80 if x_bstride is None else x_bstride), (B if x_mod is None else x_mod), _p(mu), _p(spks), _p(cond), B, T, 80, _p(h), i64(h.shape[-1]), dtype, stream()),
-          "mmx_est_pack")
+    call("mmx_est_pack", _p(x), T * 80 if x_bstride is None else x_bstride, B if x_mod is None else x_mod, _p(mu), _p(spks),
+         _p(cond), B, T, 80, _p(h), h.shape[-1], dtype, stream())
 
 
 def sinusoidal_emb(t, out, *, dim, dtype, scale=1000.0):
-    check(load().mmx_sinusoidal_emb(_p(t), t.numel(), dim, C.c_float(scale), _p(out), dtype, stream()),
-          "mmx_sinusoidal_emb")
+    call("mmx_sinusoidal_emb", _p(t), t.numel(), dim, scale, _p(out), dtype, stream())
 
 
 def cfg_euler(x, d_cond, d_uncond, cfg, dt, n):
-    check(load().mmx_cfg_euler(_p(x), _p(d_cond), _p(d_uncond), C.c_float(cfg), C.c_float(dt), i64(n), stream()),
-          "mmx_cfg_euler")
+    call("mmx_cfg_euler", _p(x), _p(d_cond), _p(d_uncond), cfg, dt, n, stream())
 
 
 def conv_cin1(x, w, bias, *, T, C_, k, batch, dtype, slope=0.1, alpha=None, out_f32=None, out_act=None):
-    check(load().mmx_conv_cin1(_p(x), i64(T), T, C_, k, _p(w), _p(bias), C.c_float(slope), _p(alpha), _p(out_f32), _p(out_act),
-                               batch, dtype, stream()), "mmx_conv_cin1")
+    call("mmx_conv_cin1", _p(x), T, T, C_, k, _p(w), _p(bias), slope, _p(alpha), _p(out_f32), _p(out_act), batch, dtype, stream())
 
 
 def vae_sample(ml, noise, z, m, logs, *, rows, D):
-    check(load().mmx_vae_sample(_p(ml), _p(noise), i64(rows), D, _p(z), _p(m), _p(logs), stream()), "mmx_vae_sample")
+    call("mmx_vae_sample", _p(ml), _p(noise), rows, D, _p(z), _p(m), _p(logs), stream())
 
 
 def prefetch4(tensors, sink, workgroups=128):
     """mmx_prefetch4: leaves the bytes of up to four tensors in L2 / the Infinity Cache (a side stream of the LM decode step)."""
     t = list(tensors) + [None] * (4 - len(tensors))
     nb = lambda x: 0 if x is None else (x.numel() * x.element_size()) // 16 * 16
-    check(load().mmx_prefetch4(_p(t[0]), i64(nb(t[0])), _p(t[1]), i64(nb(t[1])), _p(t[2]), i64(nb(t[2])), _p(t[3]), i64(nb(t[3])),
-                               _p(sink), workgroups, stream()), "mmx_prefetch4")
+    call("mmx_prefetch4", _p(t[0]), nb(t[0]), _p(t[1]), nb(t[1]), _p(t[2]), nb(t[2]), _p(t[3]), nb(t[3]), _p(sink), workgroups,
+         stream())
 
 
 def resample_linear(x, T2):
@@ -226,13 +219,13 @@ def resample_linear(x, T2):
     x = x.contiguous()
     T = x.shape[-1]
     out = torch.empty(*x.shape[:-1], T2, dtype=torch.float32, device=x.device)
-    check(load().mmx_resample_linear(_p(x), i64(x.numel() // T), T, T2, _p(out), stream()), "mmx_resample_linear")
+    call("mmx_resample_linear", _p(x), x.numel() // T, T, T2, _p(out), stream())
     return out
 
 
 def conv_cout1_tanh(act, w, bias, out, *, T, C_, k, batch, dtype, slope=0.1, use_tanh=True):
-    check(load().mmx_conv_cout1_tanh(_p(act), i64(T * C_), T, C_, k, _p(w), _p(bias), C.c_float(slope), int(use_tanh),
-                                     _p(out), i64(T), batch, dtype, stream()), "mmx_conv_cout1_tanh")
+    call("mmx_conv_cout1_tanh", _p(act), T * C_, T, C_, k, _p(w), _p(bias), slope, int(use_tanh), _p(out), T, batch, dtype,
+         stream())
 
 
 # ----------------------------------------------------------------------------- fused estimator row-tile kernels
@@ -254,8 +247,7 @@ def est_tail(ao, x, w, *, B, T, dtype, bm, rowmask=None, act_out=None, act_ld=0,
         p.next = nxt
     if isinstance(w["wo_p"], Planed):                   # [hi pack | lo pack] weights (pack_skinny with X2W), the next block's too
         dtype = L.X2W
-    check(load().mmx_est_tail(C.byref(p), C.c_int(dtype), C.c_int(bm), C.c_int(pf + 16 * waves + (512 if narrow else 0)), stream()),
-          "mmx_est_tail")
+    call("mmx_est_tail", C.byref(p), dtype, bm, pf + 16 * waves + (512 if narrow else 0), stream())
 
 
 def est_resnet(a_in, lda, cin, x, r, tv, tv_bs, *, B, T, dtype, bm, rowmask=None, nxt=None, eps=1e-5, pf=0, t_begin=0,
@@ -268,7 +260,7 @@ def est_resnet(a_in, lda, cin, x, r, tv, tv_bs, *, B, T, dtype, bm, rowmask=None
         p.next = nxt
     if isinstance(r["w1_p"], Planed):
         dtype = L.X2W
-    check(load().mmx_est_resnet(C.byref(p), C.c_int(dtype), C.c_int(bm), C.c_int(pf + 16 * waves), stream()), "mmx_est_resnet")
+    call("mmx_est_resnet", C.byref(p), dtype, bm, pf + 16 * waves, stream())
 
 
 # ----------------------------------------------------------------------------- fused DAC ResidualUnit
@@ -292,35 +284,31 @@ def dac_ru(x, x_out, ru, *, B, T, C_, dil, dtype, act_out=None, alpha_next=None,
                       B=B, T=T, C=C_, dil=dil, slope=slope)
     if isinstance(ru["w7_p"], Planed):
         dtype = L.X2W
-    check(load().mmx_dac_ru(C.byref(p), C.c_int(dtype), C.c_int(bm), stream()), "mmx_dac_ru")
+    call("mmx_dac_ru", C.byref(p), dtype, bm, stream())
 
 
 # ----------------------------------------------------------------------------- attention
 def attn_dense(q, k, v, out, *, B, H, Tq, Tk, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, dtype,
                keymask=None, chunk=0, pos=None, ldp=0, pos_u=None, pos_v=None, head_stride=0, q_begin=0, km_bs=None):
-    check(load().mmx_attn_dense(_p(q), i64(ldq), i64(q_bs), _p(k), i64(ldk), i64(k_bs), _p(v), i64(ldv), i64(v_bs),
-                                _p(out), i64(ldo), i64(o_bs), B, H, 64, Tq, Tk, C.c_float(scale), _p(keymask),
-                                i64(Tk if km_bs is None else km_bs), chunk, _p(pos), i64(ldp), _p(pos_u), _p(pos_v), head_stride,
-                                q_begin, dtype, stream()),
-          "mmx_attn_dense")
+    call("mmx_attn_dense", _p(q), ldq, q_bs, _p(k), ldk, k_bs, _p(v), ldv, v_bs, _p(out), ldo, o_bs, B, H, 64, Tq, Tk, scale,
+         _p(keymask), Tk if km_bs is None else km_bs, chunk, _p(pos), ldp, _p(pos_u), _p(pos_v), head_stride, q_begin, dtype,
+         stream())
 
 
 def attn_relpos_bf16(q, k, vt, pos, pos_u, pos_v, out, *, B, H, T, ldq, ldk, ldvt, ldp, ldo, q_bs, k_bs, vt_bs, o_bs, scale, chunk=0,
                      klen=None):
     if klen is not None:
         assert klen.dtype == torch.int32 and klen.numel() >= B
-    check(load().mmx_attn_relpos_bf16(_p(q), i64(ldq), i64(q_bs), _p(k), i64(ldk), i64(k_bs), _p(vt), i64(ldvt), i64(vt_bs),
-                                      _p(pos), i64(ldp), _p(pos_u), _p(pos_v), _p(out), i64(ldo), i64(o_bs), B, H, T,
-                                      C.c_float(scale), chunk, _p(klen), stream()), "mmx_attn_relpos_bf16")
+    call("mmx_attn_relpos_bf16", _p(q), ldq, q_bs, _p(k), ldk, k_bs, _p(vt), ldvt, vt_bs, _p(pos), ldp, _p(pos_u), _p(pos_v),
+         _p(out), ldo, o_bs, B, H, T, scale, chunk, _p(klen), stream())
 
 
 def attn_relpos_x(q, k, v, pos, pos_u, pos_v, out, *, B, H, T, ldq, ldk, ldv, ldp, ldo, q_bs, k_bs, v_bs, o_bs, scale, chunk=0, klen=None):
     """The split build's conformer rel-pos attention on the MFMA (include/mmx_hip.h mmx_attn_relpos_x): fp32 operands."""
     if klen is not None:
         assert klen.dtype == torch.int32 and klen.numel() >= B
-    check(load().mmx_attn_relpos_x(_p(q), i64(ldq), i64(q_bs), _p(k), i64(ldk), i64(k_bs), _p(v), i64(ldv), i64(v_bs), _p(pos), i64(ldp),
-                                   _p(pos_u), _p(pos_v), _p(out), i64(ldo), i64(o_bs), B, H, T, C.c_float(scale), chunk, _p(klen), stream()),
-          "mmx_attn_relpos_x")
+    call("mmx_attn_relpos_x", _p(q), ldq, q_bs, _p(k), ldk, k_bs, _p(v), ldv, v_bs, _p(pos), ldp, _p(pos_u), _p(pos_v), _p(out),
+         ldo, o_bs, B, H, T, scale, chunk, _p(klen), stream())
 
 
 def attn_flash_bf16(q, k, vt, out, *, B, H, T, ldq, ldk, ldvt, ldo, q_bs, k_bs, vt_bs, o_bs, scale, keymask=None,
@@ -329,13 +317,11 @@ def attn_flash_bf16(q, k, vt, out, *, B, H, T, ldq, ldk, ldvt, ldo, q_bs, k_bs, 
     if klen is not None:
         assert klen.dtype == torch.int32 and klen.numel() >= B
     if fp8:
-        check(load().mmx_attn_flash_fp8(_p(q), i64(ldq), i64(q_bs), _p(k), i64(ldk), i64(k_bs), _p(vt), i64(ldvt),
-                                        i64(vt_bs), _p(out), i64(ldo), i64(o_bs), B, H, T, C.c_float(scale),
-                                        _p(keymask), i64(T if km_bs is None else km_bs), chunk, q_begin, _p(klen), stream()), "mmx_attn_flash_fp8")
+        call("mmx_attn_flash_fp8", _p(q), ldq, q_bs, _p(k), ldk, k_bs, _p(vt), ldvt, vt_bs, _p(out), ldo, o_bs, B, H, T, scale,
+             _p(keymask), T if km_bs is None else km_bs, chunk, q_begin, _p(klen), stream())
         return
-    check(load().mmx_attn_flash_bf16(_p(q), i64(ldq), i64(q_bs), _p(k), i64(ldk), i64(k_bs), _p(vt), i64(ldvt),
-                                     i64(vt_bs), _p(out), i64(ldo), i64(o_bs), B, H, T, C.c_float(scale),
-                                     _p(keymask), i64(T if km_bs is None else km_bs), chunk, q_begin, _p(klen), stream()), "mmx_attn_flash_bf16")
+    call("mmx_attn_flash_bf16", _p(q), ldq, q_bs, _p(k), ldk, k_bs, _p(vt), ldvt, vt_bs, _p(out), ldo, o_bs, B, H, T, scale,
+         _p(keymask), T if km_bs is None else km_bs, chunk, q_begin, _p(klen), stream())
 
 
 def attn_flash_x(q, k, v, out, *, B, H, T, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, scale, keymask=None, chunk=0, q_begin=0,
@@ -343,9 +329,8 @@ def attn_flash_x(q, k, v, out, *, B, H, T, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs,
     """The split build's flash attention: fp32 q / k / v (V row-major) and fp32 out (include/mmx_hip.h)."""
     if klen is not None:
         assert klen.dtype == torch.int32 and klen.numel() >= B
-    check(load().mmx_attn_flash_x(_p(q), i64(ldq), i64(q_bs), _p(k), i64(ldk), i64(k_bs), _p(v), i64(ldv), i64(v_bs),
-                                  _p(out), i64(ldo), i64(o_bs), B, H, T, C.c_float(scale), _p(keymask),
-                                  i64(T if km_bs is None else km_bs), chunk, q_begin, _p(klen), stream()), "mmx_attn_flash_x")
+    call("mmx_attn_flash_x", _p(q), ldq, q_bs, _p(k), ldk, k_bs, _p(v), ldv, v_bs, _p(out), ldo, o_bs, B, H, T, scale,
+         _p(keymask), T if km_bs is None else km_bs, chunk, q_begin, _p(klen), stream())
 
 
 def attn_flash_xs(qk, vt, out, *, B, H, T, ldqk, ldvt, ldo, qk_bs, vt_bs, o_bs, scale, keymask=None, chunk=0, q_begin=0, km_bs=None,
@@ -354,9 +339,8 @@ def attn_flash_xs(qk, vt, out, *, B, H, T, ldqk, ldvt, ldo, qk_bs, vt_bs, o_bs, 
     form: 0 = workgroup shape chosen per launch, 1 = the co-residency-friendly shape (launches beside the decode loop)."""
     if klen is not None:
         assert klen.dtype == torch.int32 and klen.numel() >= B
-    check(load().mmx_attn_flash_xs(_p(qk), i64(ldqk), i64(qk_bs), _p(vt), i64(ldvt), i64(vt_bs), _p(out), i64(ldo), i64(o_bs), B, H, T,
-                                   C.c_float(scale), _p(keymask), i64(T if km_bs is None else km_bs), chunk, q_begin, _p(klen), int(form),
-                                   stream()), "mmx_attn_flash_xs")
+    call("mmx_attn_flash_xs", _p(qk), ldqk, qk_bs, _p(vt), ldvt, vt_bs, _p(out), ldo, o_bs, B, H, T, scale, _p(keymask),
+         T if km_bs is None else km_bs, chunk, q_begin, _p(klen), int(form), stream())
 
 
 # ----------------------------------------------------------------------------- LM decode
@@ -373,8 +357,7 @@ def pack_skinny(w, *, dtype, kscale=None, interleave_half=0):
     KB = 32 if L.WEIGHT_DT[dtype] == torch.bfloat16 else 16
     tiles = (N + 15) // 16
     wp = torch.empty(tiles * (K // KB) * 64 * (KB // 4), dtype=L.WEIGHT_DT[dtype], device=w.device)
-    check(load().mmx_pack_skinny(_p(w), i64(w.stride(0)), N, K, _p(kscale), interleave_half, _p(wp), dtype, stream()),
-          "mmx_pack_skinny")
+    call("mmx_pack_skinny", _p(w), w.stride(0), N, K, _p(kscale), interleave_half, _p(wp), dtype, stream())
     return wp
 
 
@@ -408,10 +391,8 @@ def skinny_gemm(x, wp, *, B, K, N, dtype, bias=None, rs=False, eps=1e-6, epi=0, 
     """kgamma (split builds only): the RMSNorm gain [K], applied to x in the kernel instead of being folded into wp."""
     xdt = L.dt_of(x)
     flags = (X_PACKED if x_packed else 0) | (OUT_PACKED if out_packed else 0)
-    check(load().mmx_skinny_gemm(_p(x), xdt, i64(ldx if ldx is not None else K), B, K, N, _p(wp), _p(bias), int(rs),
-                                 C.c_float(eps), epi, _p(out_f32), i64(ldo_f if ldo_f is not None else N),
-                                 _p(out_act), i64(ldo_a if ldo_a is not None else N), dtype, flags, _p(kgamma), stream()),
-          "mmx_skinny_gemm")
+    call("mmx_skinny_gemm", _p(x), xdt, ldx if ldx is not None else K, B, K, N, _p(wp), _p(bias), int(rs), eps, epi, _p(out_f32),
+         ldo_f if ldo_f is not None else N, _p(out_act), ldo_a if ldo_a is not None else N, dtype, flags, _p(kgamma), stream())
 
 
 SSQ_SLOTS = 64
@@ -459,8 +440,8 @@ def pack_skinny_h2(w, *, planes=1, interleave_half=0):
 
 
 def decode_prep(x, xs, ssq, *, B, K, gamma=None, h=None, dtype=L.X3):
-    check(load().mmx_decode_prep(_p(x), i64(x.shape[-1]), B, K, _p(gamma), _p(h), i64(h.shape[-1] if h is not None else 0), _p(xs),
-                                 _p(ssq), dtype, stream()), "mmx_decode_prep")
+    call("mmx_decode_prep", _p(x), x.shape[-1], B, K, _p(gamma), _p(h), h.shape[-1] if h is not None else 0, _p(xs), _p(ssq), dtype,
+         stream())
 
 
 def skinny2(xs, wp, *, B, K, N, dtype, bias=None, ssq_in=None, eps=1e-6, epi=0, out=None, ldo=None, xs_out=None, gamma_next=None,
@@ -468,9 +449,9 @@ def skinny2(xs, wp, *, B, K, N, dtype, bias=None, ssq_in=None, eps=1e-6, epi=0, 
     """The split build's decode-step projection on split-plane activations (include/mmx_hip.h mmx_skinny2)."""
     if isinstance(wp, Planed):
         dtype = L.H2W if dtype in (L.H2, L.H2W) else L.X3W
-    check(load().mmx_skinny2(_p(xs), B, K, N, _p(wp), _p(bias), _p(ssq_in), C.c_float(eps), epi, _p(out),
-                             i64(ldo if ldo is not None else N), _p(xs_out), _p(gamma_next), _p(ssq_out), tiles_per_wg, ksplit,
-                             _p(part), i64(part.numel() if part is not None else 0), _p(tickets), dtype, stream()), "mmx_skinny2")
+    call("mmx_skinny2", _p(xs), B, K, N, _p(wp), _p(bias), _p(ssq_in), eps, epi, _p(out), ldo if ldo is not None else N, _p(xs_out),
+         _p(gamma_next), _p(ssq_out), tiles_per_wg, ksplit, _p(part), part.numel() if part is not None else 0, _p(tickets), dtype,
+         stream())
 
 
 def rope_kv_store(qkv, inv_freq, pos, q_out, kc, vc, block_table, *, B, rows, Hq, Hkv, page, dtype, ldqkv=None, qkv_bs=None,
@@ -478,18 +459,17 @@ def rope_kv_store(qkv, inv_freq, pos, q_out, kc, vc, block_table, *, B, rows, Hq
     """ldqkv / ldq: row pitches of qkv / q_out in elements (default: dense), qkv_bs / q_bs: their batch strides (default: rows * pitch)."""
     ldqkv = (Hq + 2 * Hkv) * 64 if ldqkv is None else ldqkv
     ldq = Hq * 64 if ldq is None else ldq
-    check(load().mmx_rope_kv_store(_p(qkv), i64(ldqkv), i64(rows * ldqkv if qkv_bs is None else qkv_bs), B, rows, Hq, Hkv, 64,
-                                   _p(inv_freq), _p(pos), _p(q_out), i64(ldq), i64(rows * ldq if q_bs is None else q_bs), _p(kc), _p(vc),
-                                   _p(block_table), block_table.shape[1], page, dtype, stream()), "mmx_rope_kv_store")
+    call("mmx_rope_kv_store", _p(qkv), ldqkv, rows * ldqkv if qkv_bs is None else qkv_bs, B, rows, Hq, Hkv, 64, _p(inv_freq), _p(pos),
+         _p(q_out), ldq, rows * ldq if q_bs is None else q_bs, _p(kc), _p(vc), _p(block_table), block_table.shape[1], page, dtype,
+         stream())
 
 
 def paged_attn(q, pos, kc, vc, block_table, out, *, B, rows, Hq, Hkv, page, dtype, ldq=None, q_bs=None, ldo=None, o_bs=None):
     """ldq / ldo: row pitches of q / out in elements (default: dense), q_bs / o_bs: their batch strides (default: rows * pitch)."""
     ldq = Hq * 64 if ldq is None else ldq
     ldo = Hq * 64 if ldo is None else ldo
-    check(load().mmx_paged_attn(_p(q), i64(ldq), i64(rows * ldq if q_bs is None else q_bs), B, rows, Hq, Hkv, 64, C.c_float(0.125),
-                                _p(pos), _p(kc), _p(vc), _p(block_table), block_table.shape[1], page, _p(out),
-                                i64(ldo), i64(rows * ldo if o_bs is None else o_bs), dtype, stream()), "mmx_paged_attn")
+    call("mmx_paged_attn", _p(q), ldq, rows * ldq if q_bs is None else q_bs, B, rows, Hq, Hkv, 64, 0.125, _p(pos), _p(kc), _p(vc),
+         _p(block_table), block_table.shape[1], page, _p(out), ldo, rows * ldo if o_bs is None else o_bs, dtype, stream())
 
 
 def decode_attn_bits(out_packed=False, per_head=False, out_split=False, one_head=False):
@@ -507,21 +487,20 @@ def decode_attn(qkv, inv_freq, pos, kc, vc, block_table, out, *, B, Hq, Hkv, pag
     ldqkv / ldo: row pitches of qkv / a row-major `out` in elements (default: dense).
     finished: int32 [B] or None; the workgroups of a sequence whose flag is set return at once (mmx_decode_attn_fin)."""
     assert finished is None or (finished.dtype == torch.int32 and finished.numel() >= B and finished.stride(-1) == 1)
-    check(load().mmx_decode_attn_fin(_p(qkv), i64((Hq + 2 * Hkv) * 64 if ldqkv is None else ldqkv), B, Hq, Hkv, 64, _p(inv_freq), _p(rope_tab),
-                                     _p(pos), _p(finished), _p(kc), _p(vc), _p(block_table), block_table.shape[1], page, C.c_float(0.125), _p(out),
-                                     i64(Hq * 64 if ldo is None else ldo), dtype, decode_attn_bits(out_packed, per_head, out_split, one_head), stream()), "mmx_decode_attn_fin")
+    call("mmx_decode_attn_fin", _p(qkv), (Hq + 2 * Hkv) * 64 if ldqkv is None else ldqkv, B, Hq, Hkv, 64, _p(inv_freq), _p(rope_tab),
+         _p(pos), _p(finished), _p(kc), _p(vc), _p(block_table), block_table.shape[1], page, 0.125, _p(out),
+         Hq * 64 if ldo is None else ldo, dtype, decode_attn_bits(out_packed, per_head, out_split, one_head), stream())
 
 
 def swiglu(gu, out, *, rows, I, dtype, ldgu=None, ldo=None):
-    check(load().mmx_swiglu(_p(gu), i64(ldgu or 2 * I), rows, I, _p(out), i64(ldo or I), dtype, stream()), "mmx_swiglu")
+    call("mmx_swiglu", _p(gu), ldgu or 2 * I, rows, I, _p(out), ldo or I, dtype, stream())
 
 
 def sample_step(logits, state, out_tokens, speech_emb, next_x, *, V, B, eos_id, seed, top_k=25, top_p=0.8,
                 win_size=10, tau_r=0.1, sampled=None, forced=None, logp_out=None):
-    check(load().mmx_sample_step(_p(logits), i64(logits.shape[-1]), V, B, eos_id, top_k, C.c_float(top_p), win_size,
-                                 C.c_float(tau_r), C.c_uint64(seed), _p(state), _p(out_tokens), out_tokens.shape[1],
-                                 _p(sampled), _p(forced), _p(speech_emb), speech_emb.shape[1], _p(next_x),
-                                 i64(next_x.shape[-1]), _p(logp_out), stream()), "mmx_sample_step")
+    call("mmx_sample_step", _p(logits), logits.shape[-1], V, B, eos_id, top_k, top_p, win_size, tau_r, seed, _p(state),
+         _p(out_tokens), out_tokens.shape[1], _p(sampled), _p(forced), _p(speech_emb), speech_emb.shape[1], _p(next_x),
+         next_x.shape[-1], _p(logp_out), stream())
 
 
 SAMP_MODE, SAMP_TOP_K, SAMP_WIN, SAMP_TOP_P, SAMP_TAU_R, SAMP_SEED_LO, SAMP_SEED_HI = range(7)   # fields of the sampler table
@@ -544,6 +523,5 @@ def sampler_column(mode=0, top_p=0.8, top_k=25, win_size=10, tau_r=0.1, seed=0):
 def sample_step_tab(logits, state, out_tokens, speech_emb, next_x, samp, *, V, B, eos_id, sampled=None, forced=None, logp_out=None):
     """mmx_sample_step with every sequence's sampler in the device table samp int32 [8, B] (sampler_column per column)."""
     assert samp.dtype == torch.int32 and samp.is_contiguous() and samp.shape == (8, B)
-    check(load().mmx_sample_step_tab(_p(logits), i64(logits.shape[-1]), V, B, eos_id, _p(samp), _p(state), _p(out_tokens),
-                                     out_tokens.shape[1], _p(sampled), _p(forced), _p(speech_emb), speech_emb.shape[1],
-                                     _p(next_x), i64(next_x.shape[-1]), _p(logp_out), stream()), "mmx_sample_step_tab")
+    call("mmx_sample_step_tab", _p(logits), logits.shape[-1], V, B, eos_id, _p(samp), _p(state), _p(out_tokens), out_tokens.shape[1],
+         _p(sampled), _p(forced), _p(speech_emb), speech_emb.shape[1], _p(next_x), next_x.shape[-1], _p(logp_out), stream())

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import clips as CL
-from ._lib import MmxError, check, i64, load, stream, _p
+from ._lib import MmxError, call, stream, _p
 
 NOUT = 1024                                              # include/mmx_hip.h MMX_RESAMPLE_NOUT: outputs per workgroup
 
@@ -129,9 +129,8 @@ class Resample:
         if cols > 2 ** 31 - 1 - NOUT:
             raise MmxError(f"mmx_resample_sinc: {cols} output samples per clip do not fit the entry point's 32-bit column count")
         out = torch.empty(B, cols, dtype=torch.float32, device=wave.device)
-        check(load().mmx_resample_sinc(_p(wave), CL.row_stride(wave), L, B, _p(d_lens), h_lens, self.o, self.n,
-                                       self._host[3], _p(taps), _p(first), _p(count), taps.shape[0], _p(out), i64(cols), cols, stream()),
-              "mmx_resample_sinc")
+        call("mmx_resample_sinc", _p(wave), CL.row_stride(wave), L, B, _p(d_lens), h_lens, self.o, self.n, self._host[3], _p(taps),
+             _p(first), _p(count), taps.shape[0], _p(out), cols, cols, stream())
         return out
 
     @torch.no_grad()

@@ -14,7 +14,7 @@ import torch
 
 from . import mel as MEL
 from . import ops
-from ._lib import BF16, F32, X2, X2W, MmxError, check, i64, is_split, load, stream, _p
+from ._lib import BF16, F32, X2, X2W, MmxError, call, is_split, stream, _p
 from .clips import on_device, pack
 
 SAMPLE_RATE, N_FFT, HOP, N_MELS = 16000, 400, 160, 128
@@ -103,8 +103,8 @@ def s3_rope_fsmn(qkv, x, r, wt, rope_cos, rope_sin, *, B, T, C_, lens=None):
     """mmx_s3_rope_fsmn: qkv fp32 [B, T, 3C] (q and k rotated in place), x / r fp32 [B, T, C], wt fp32 [31, C], lens int32 [B]."""
     if lens is not None:
         assert lens.dtype == torch.int32 and lens.numel() >= B
-    check(load().mmx_s3_rope_fsmn(_p(qkv), i64(3 * C_), i64(T * 3 * C_), B, T, C_, _p(x), i64(T * C_), _p(r), i64(T * C_), _p(wt),
-                                  _p(rope_cos), _p(rope_sin), rope_cos.shape[0], _p(lens), stream()), "mmx_s3_rope_fsmn")
+    call("mmx_s3_rope_fsmn", _p(qkv), 3 * C_, T * 3 * C_, B, T, C_, _p(x), T * C_, _p(r), T * C_, _p(wt), _p(rope_cos), _p(rope_sin),
+         rope_cos.shape[0], _p(lens), stream())
 
 
 def fsq_encode(x, W, bias, ids, *, B, T, C_, lens=None, pre=None):
@@ -112,8 +112,7 @@ def fsq_encode(x, W, bias, ids, *, B, T, C_, lens=None, pre=None):
     if lens is not None:
         assert lens.dtype == torch.int32 and lens.numel() >= B
     assert ids.dtype == torch.int32 and W.dtype == torch.float32 and tuple(W.shape) == (8, C_)
-    check(load().mmx_fsq_encode(_p(x), i64(C_), i64(T * C_), B, T, C_, _p(W), _p(bias), _p(lens), _p(ids), i64(T), _p(pre), stream()),
-          "mmx_fsq_encode")
+    call("mmx_fsq_encode", _p(x), C_, T * C_, B, T, C_, _p(W), _p(bias), _p(lens), _p(ids), T, _p(pre), stream())
 
 
 # ----------------------------------------------------------------------------- engine

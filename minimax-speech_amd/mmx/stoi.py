@@ -37,7 +37,7 @@ import torch
 from . import clips as CL
 from . import mel as MEL
 from . import ops
-from ._lib import MmxError, check, load, stream, _p
+from ._lib import MmxError, call, stream, _p
 from .resample import Resample
 
 FS, FRAME, HOP, NFFT, BANDS, SEG = 10000, 256, 128, 512, 15, 30
@@ -138,8 +138,8 @@ def select(ref, lens=None, d_lens=None, h_lens=None):
     cap = frames_of(L)
     out = dict(energy=torch.zeros(B, cap, dtype=torch.float64, device=ref.device), mask=torch.empty(B, cap, dtype=torch.uint8, device=ref.device),
                map=torch.empty(B, cap, dtype=torch.int32, device=ref.device), kept=torch.empty(B, dtype=torch.int32, device=ref.device), cap=cap)
-    check(load().mmx_stoi_select(_p(ref), CL.row_stride(ref), L, B, _p(d_lens), h_lens, _p(win), _p(out["energy"]), _p(out["mask"]), _p(out["map"]),
-                                 _p(out["kept"]), cap, stream()), "mmx_stoi_select")
+    call("mmx_stoi_select", _p(ref), CL.row_stride(ref), L, B, _p(d_lens), h_lens, _p(win), _p(out["energy"]), _p(out["mask"]),
+         _p(out["map"]), _p(out["kept"]), cap, stream())
     return out
 
 
@@ -154,8 +154,8 @@ def bands(est, ref, lens, sel, d_lens=None, h_lens=None):
     basis, filt, win = _device_tables(ref.device)
     cap = sel["cap"]
     env = torch.zeros(B, 2, cap, 16, dtype=torch.float32, device=ref.device)
-    check(load().mmx_stoi_bands(_p(est), CL.row_stride(est), _p(ref), CL.row_stride(ref), L, B, _p(d_lens), h_lens, _p(win), _p(sel["map"]), _p(sel["kept"]),
-                                _p(basis), _p(filt), _p(env), cap, stream()), "mmx_stoi_bands")
+    call("mmx_stoi_bands", _p(est), CL.row_stride(est), _p(ref), CL.row_stride(ref), L, B, _p(d_lens), h_lens, _p(win), _p(sel["map"]),
+         _p(sel["kept"]), _p(basis), _p(filt), _p(env), cap, stream())
     return env
 
 
@@ -166,7 +166,7 @@ def score(env, kept, extended=False):
     work = torch.empty(B, wcap, dtype=torch.float64, device=env.device)
     out = torch.empty(B, dtype=torch.float64, device=env.device)
     frames = torch.empty(B, dtype=torch.int32, device=env.device)
-    check(load().mmx_stoi_score(_p(env), cap, B, _p(kept), int(bool(extended)), _p(work), wcap, _p(out), _p(frames), stream()), "mmx_stoi_score")
+    call("mmx_stoi_score", _p(env), cap, B, _p(kept), int(bool(extended)), _p(work), wcap, _p(out), _p(frames), stream())
     return out, frames
 
 

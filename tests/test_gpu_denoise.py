@@ -207,7 +207,7 @@ def test_identities(n):
 def test_refusals_launch_nothing(monkeypatch):
     from mmx import denoise as D
     x = H.clip(24000, 7).cuda()
-    monkeypatch.setattr(D, "load", lambda: pytest.fail("a refused call reached the library"))
+    monkeypatch.setattr(D, "call", lambda *a: pytest.fail("a refused call reached the library"))
     monkeypatch.setattr(D, "_device_tables", lambda *a: pytest.fail("a refused call built tables"))
     for bad in (dict(win_length=2048, hop_length=256), dict(win_length=2000, hop_length=500), dict(win_length=4096, hop_length=1024)):
         with pytest.raises(D.MmxError):
